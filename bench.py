@@ -7,7 +7,14 @@ caller's QP step (biped_pympc/convex_mpc/mpc_controller_cusadi.py:99-169) at BAS
 4096-env shard (weak scaling) and the first-stage inputs u0 (12 doubles/env, the only thing the
 wrapper consumes, mpc_controller_cusadi.py:186) are gathered over RCCL.
 
-Usage: python bench.py [--gpus N --steps K --warmup W]
+Usage: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+  A plain run sets up, runs W untimed and K timed steps and prints the headline figures
+  (metric, value, unit, ms_per_step, ...). --full adds every other leg to the same line: per-kernel
+  event timings, roofline, controller step, drop-in schedule, sustained rate, config 3, CPU baseline,
+  parity against the oracle and the per-rank spread (the --no-* / --kernel-reps / --cpu-* /
+  --sustain-seconds options shape those legs and have no effect without --full).
+  --dump-outputs DIR: rank 0 writes what the last timed step returned, DIR/u0.npy (u0 of every env,
+  global env order, float64), and the solution it was cut from, DIR/x_local.npy (rank 0's shard).
   --gpus N > 1 without an external launcher: this process starts N ranks itself (one child process
   per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT in their
   environment), touches no GPU itself, and exits with the first failing rank's status. Under
@@ -74,7 +81,30 @@ def parse(argv=None):
                    help="skip the BASELINE config-3 leg (fused N = 20, B = 4096, K = 10 kernel + oracle sample)")
     p.add_argument("--dump-u0", default=None,
                    help="rank 0 saves the gathered u0 (global env order) of the last timed step as .npy")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="rank 0 saves the last timed step's outputs as DIR/u0.npy and DIR/x_local.npy (float64)")
+    p.add_argument("--full", action="store_true",
+                   help="also run every leg beside the timed steps (per-kernel timings, roofline, controller "
+                        "step, drop-in schedule, sustained rate, config 3, CPU baseline, parity, rank spread)")
     return p.parse_args(argv)
+
+
+def dump_outputs(path: str, u0, x_local) -> None:
+    """--dump-outputs: what the caller of the timed step received (u0 of every env) and rank 0's
+    solution x it is a slice of, as float64 .npy (B = 4096, N = 10: 0.4 MB + 7.9 MB). Each array
+    is held to DUMP_BYTES / 2: a larger one is cut to a sorted sample of its rows drawn with a fixed
+    seed, which depends on its shape alone (two builds dump the same rows)."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in (("u0", u0), ("x_local", x_local)):
+        rows = max(1, (DUMP_BYTES // 2) // (8 * t.shape[1]))
+        if t.shape[0] > rows:
+            keep = np.sort(np.random.default_rng(0).choice(t.shape[0], rows, replace=False))
+            t = t[torch.from_numpy(keep).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(t.cpu().numpy(), dtype=np.float64))
+
+
+DUMP_BYTES = 64 * 10**6  # --dump-outputs writes at most this much in all
+CLOCK_RAMP_LAUNCHES = 36  # untimed launches of the step before a plain run's warm-up (see main)
 
 
 def _free_port() -> int:
@@ -306,15 +336,20 @@ def hook_main(a, hook, dist, world, rank, N, K, B, d):
     solve = load_solve_hook(hook)(N, K)
     sh = ShardedMPC(N, K, world * B, device=dev, y0=1.0, solve_fn=solve)
     elapsed, u0_last, own = run_timed(sh, inputs, a, dist, world, dev)
-    t1 = time.perf_counter()
-    x = solve(inputs)
-    solve_ms = 1e3 * (time.perf_counter() - t1)
-    t1 = time.perf_counter()
-    sh.gather_u0(x[:, 12 * N:12 * N + 12])
-    ranks = rank_spread(dist, dev, solve_ms, 1e3 * (time.perf_counter() - t1), own)
-    if rank == 0:
+    if rank == 0:  # before the --full leg below, whose gather writes u0_all again
         if a.dump_u0:
             np.save(a.dump_u0, u0_last.numpy())
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, u0_last, sh.x_local)
+    ranks = None
+    if a.full:
+        t1 = time.perf_counter()
+        x = solve(inputs)
+        solve_ms = 1e3 * (time.perf_counter() - t1)
+        t1 = time.perf_counter()
+        sh.gather_u0(x[:, 12 * N:12 * N + 12])
+        ranks = rank_spread(dist, dev, solve_ms, 1e3 * (time.perf_counter() - t1), own)
+    if rank == 0:
         emit({
             "metric": f"batched SRBD QP solves/sec (N={N}, {K} PDIPM iters)", "value": round(world * B * a.steps / elapsed, 1),
             "unit": "solves/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -323,7 +358,7 @@ def hook_main(a, hook, dist, world, rank, N, K, B, d):
             "config": {"workload": f"CPU solve hook {hook} (launcher test; not a GPU measurement)",
                        "batch_per_gpu": B, "global_batch": B * world, "horizon": N, "pdipm_iters": K,
                        "parallelism": f"dp{world}" + (" (u0 all_gather over gloo)" if world > 1 else "")},
-            "ranks": ranks})
+            **({"ranks": ranks} if a.full else {})})
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
@@ -479,25 +514,60 @@ def main(argv=None):
     inputs = [torch.from_numpy(x).to(dev) for x in wl.inputs]
     sh = ShardedMPC(N, K, world * B, device=dev, y0=1.0)
 
-    # per-kernel timing (HIP events on the launch stream) BEFORE the timed steps, on buffers of their
-    # own: the driver's short runs (--warmup 5) otherwise time the first steps while the GPU's clocks
-    # are still ramping up from idle (round 2: 0.687 ms per step at 20 steps vs 0.664 ms at 100)
-    bufs = solver.MPCSolveBuffers.allocate(N, B, dev)
-    qp = bufs.qp_views()
-    sol_qp = [qp[0], qp[4], qp[2], qp[1], qp[5], qp[3]]  # H, G, A, f, h(=d), b
-    pd_out = solver._alloc_solver_outputs(B, N, dev)
-    ms_former = event_time_ms(lambda: solver.qp_former(inputs, N, outputs=qp), a.kernel_reps)
-    ms_pdipm = event_time_ms(lambda: solver.pdipm(sol_qp, None, N, K, 1.0, outputs=pd_out),
-                             a.kernel_reps)
-    # the step's own kernel: fused former + solver (one launch at every horizon), on the same inputs
-    ms_fused = event_time_ms(lambda: solver.mpc_solve(inputs, N, K, 1.0, buffers=bufs), a.kernel_reps)
-    del pd_out
+    if a.full:
+        # per-kernel timing (HIP events on the launch stream) BEFORE the timed steps, on buffers of their
+        # own: the driver's short runs (--warmup 5) otherwise time the first steps while the GPU's clocks
+        # are still ramping up from idle (round 2: 0.687 ms per step at 20 steps vs 0.664 ms at 100)
+        bufs = solver.MPCSolveBuffers.allocate(N, B, dev)
+        qp = bufs.qp_views()
+        sol_qp = [qp[0], qp[4], qp[2], qp[1], qp[5], qp[3]]  # H, G, A, f, h(=d), b
+        pd_out = solver._alloc_solver_outputs(B, N, dev)
+        ms_former = event_time_ms(lambda: solver.qp_former(inputs, N, outputs=qp), a.kernel_reps)
+        ms_pdipm = event_time_ms(lambda: solver.pdipm(sol_qp, None, N, K, 1.0, outputs=pd_out),
+                                 a.kernel_reps)
+        # the step's own kernel: fused former + solver (one launch at every horizon), on the same inputs
+        ms_fused = event_time_ms(lambda: solver.mpc_solve(inputs, N, K, 1.0, buffers=bufs), a.kernel_reps)
+        del pd_out
+    else:
+        # a plain run has no event legs in front of its steps: as many untimed launches of the step
+        # as those legs make (3 x (2 + 10)) bring the clocks up from idle, so that a short run
+        # (--steps 20 --warmup 5) times the same steady state as it does with --full (measured
+        # without them: 0.625-0.632 ms per step against 0.608)
+        for _ in range(CLOCK_RAMP_LAUNCHES):
+            sh.step(inputs)
 
     elapsed, u0_last, own_elapsed = run_timed(sh, inputs, a, dist, world, dev)
     ms_step = 1e3 * elapsed / a.steps
     value = world * B * a.steps / elapsed
     if rank == 0 and a.dump_u0:
         np.save(a.dump_u0, u0_last.cpu().numpy())
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, u0_last, sh.x_local)
+    head = {
+        "metric": "batched SRBD QP solves/sec (N=10, 10 PDIPM iters)" if (N, K) == (10, 10)
+        else f"batched SRBD QP solves/sec (N={N}, {K} PDIPM iters)",
+        "value": round(value, 1), "unit": "solves/s", "n_gpus": world, "steps": a.steps,
+        "warmup": a.warmup, "ms_per_step": round(ms_step, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"SRBD MPC QP step: qp_former + {K}-iteration sparse PDIPM, "
+                               f"batch {B}/GPU, horizon N={N}"
+                               + (", randomized gait" if a.random_gait else ", standing gait"),
+                   "batch_per_gpu": B, "global_batch": B * world, "horizon": N,
+                   "pdipm_iters": K, "qp_dims": [d.nz, d.n_eq, d.n_ineq],
+                   # the register kernels' refinement mode (srbd_set_refinement)
+                   "refinement": {0: "adaptive", 1: "every_iteration"}.get(_native.current_refinement(),
+                                                                           "policy"),
+                   "parallelism": f"dp{world}" + (f" (u0 all_gather over {'RCCL' if backend == 'nccl' else backend})"
+                                                  if world > 1 else "")},
+        "build_id": _native.build_id(),  # source hash libsrbd_mpc.so was built from (build.py)
+    }
+    if not a.full:  # a plain run: the timed steps and their figures only
+        if rank == 0:
+            emit(head)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # the step's kernel timed again at steady clocks (the legs above also serve as the clock warm-up);
     # roofline.achieved uses this figure
@@ -678,28 +748,15 @@ def main(argv=None):
         dist.barrier()  # the other ranks wait for rank 0's CPU leg before tearing down
 
     if rank == 0:
+        build_id = head.pop("build_id")
         line = {
-            "metric": "batched SRBD QP solves/sec (N=10, 10 PDIPM iters)" if (N, K) == (10, 10)
-            else f"batched SRBD QP solves/sec (N={N}, {K} PDIPM iters)",
-            "value": round(value, 1), "unit": "solves/s", "n_gpus": world, "steps": a.steps,
-            "warmup": a.warmup, "ms_per_step": round(ms_step, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"SRBD MPC QP step: qp_former + {K}-iteration sparse PDIPM, "
-                                   f"batch {B}/GPU, horizon N={N}"
-                                   + (", randomized gait" if a.random_gait else ", standing gait"),
-                       "batch_per_gpu": B, "global_batch": B * world, "horizon": N,
-                       "pdipm_iters": K, "qp_dims": [d.nz, d.n_eq, d.n_ineq],
-                       # the register kernels' refinement mode (srbd_set_refinement)
-                       "refinement": {0: "adaptive", 1: "every_iteration"}.get(_native.current_refinement(),
-                                                                               "policy"),
-                       "parallelism": f"dp{world}" + (f" (u0 all_gather over {'RCCL' if backend == 'nccl' else backend})"
-                                                      if world > 1 else "")},
+            **head,
             # solves/s without the u0 gather (every rank's shard solve alone), N > 1 only
             "value_without_gather": (round(world * B / (ms_main * 1e-3), 1) if dist is not None else None),
             "kernels_ms": {"mpc_step_fused": round(ms_fused, 4) if fused else None,
                            "qp_former": round(ms_former, 4), "pdipm": round(ms_pdipm, 4),
                            "u0_all_gather": None if ms_gather is None else round(ms_gather, 4)},
-            "build_id": _native.build_id(),  # source hash libsrbd_mpc.so was built from (build.py)
+            "build_id": build_id,
             "roofline": roofline,
             "cpu_baseline": cpu,
             "parity": parity,

@@ -4,7 +4,7 @@
 set -o pipefail
 cd /root/repo
 export TMPDIR=/tmp
-t() { SRBD_LIB=$1 timeout -k 10 120 python bench.py --horizon $2 --steps 50 --warmup 5 --no-cpu-baseline --no-controller 2>/dev/null | python -c 'import json,sys; print(json.loads(sys.stdin.read().strip().splitlines()[-1])["kernels_ms"]["mpc_step_fused"])'; }
+t() { SRBD_LIB=$1 timeout -k 10 120 python bench.py --full --horizon $2 --steps 50 --warmup 5 --no-cpu-baseline --no-controller 2>/dev/null | python -c 'import json,sys; print(json.loads(sys.stdin.read().strip().splitlines()[-1])["kernels_ms"]["mpc_step_fused"])'; }
 {
 for r in 1 2 3; do
   for H in 10 20; do

@@ -30,7 +30,7 @@ for v in variants:
     print(name, flush=True)
     subprocess.run([sys.executable, "-c", code], env=env, check=True, timeout=300)
     for N in (10, 20):
-        out = subprocess.run([sys.executable, "bench.py", "--steps", "50", "--warmup", "5", "--no-cpu-baseline",
+        out = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "50", "--warmup", "5", "--no-cpu-baseline",
                               "--horizon", str(N)], env=env, check=True, timeout=300, capture_output=True, text=True).stdout
         d = json.loads(out.strip().splitlines()[-1])
         print(f"  N={N} fused step {d['kernels_ms']['mpc_step_fused']:.4f} ms", flush=True)

@@ -34,7 +34,7 @@ def main():
     for _ in range(a.rounds):
         for name, lib in libs.items():
             r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "50", "--warmup", "10",
-                                "--no-cpu-baseline", "--horizon", str(a.horizon),
+                                "--full", "--no-cpu-baseline", "--horizon", str(a.horizon),
                                 "--batch-per-gpu", str(a.batch)],
                                env={**os.environ, "SRBD_LIB": lib}, capture_output=True, text=True, timeout=300)
             if r.returncode:

@@ -36,7 +36,7 @@ def test_launcher_starts_ranks_and_gathers_u0(tmp_path, world, B):
     N, K = 10, 3
     dump = str(tmp_path / "u0.npy")
     r = _run(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--batch-per-gpu", str(B),
-              "--iters", str(K), "--dump-u0", dump], _env(), timeout=600)
+              "--iters", str(K), "--dump-u0", dump, "--full"], _env(), timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout
@@ -70,10 +70,34 @@ def test_gpus_defaults_to_external_world_size(tmp_path):
     one-rank group here; the external launcher itself is torch.distributed.run)."""
     env = _env()
     env.update(WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_port()))
-    r = _run(["--steps", "1", "--warmup", "0", "--batch-per-gpu", "2", "--iters", "2"], env)
+    r = _run(["--steps", "1", "--warmup", "0", "--batch-per-gpu", "2", "--iters", "2", "--full"], env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["ranks"]["joined"] == 1
+
+
+def test_plain_run_prints_the_headline_and_dumps_outputs(tmp_path):
+    """Without --full: the timed steps' figures only, and --dump-outputs DIR holds the last step's u0
+    and x as float64, equal to the oracle's solve of the same seeded inputs."""
+    from oracle import oracle
+    N, K, B = 10, 2, 3
+    out = tmp_path / "dump"
+    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch-per-gpu", str(B), "--iters", str(K),
+              "--dump-outputs", str(out)], _env())
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1
+    assert line["unit"] == "solves/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(B / (line["ms_per_step"] * 1e-3), rel=1e-2)
+    assert not {"ranks", "cpu_baseline", "parity", "kernels_ms", "roofline"} & set(line)
+    assert sorted(os.listdir(out)) == ["u0.npy", "x_local.npy"]
+    x, u0 = np.load(out / "x_local.npy"), np.load(out / "u0.npy")
+    ref = oracle.mpc_solve(N, K, make_workload(B, N, seed=1000).inputs, y0=1.0, nthreads=1)[0]
+    assert x.dtype == u0.dtype == np.float64
+    assert np.array_equal(x, ref) and np.array_equal(u0, ref[:, 12 * N:12 * N + 12])
 
 
 def _port():
