@@ -34,6 +34,10 @@ def lib() -> ctypes.CDLL:
         raise NativeLibraryMissing(
             f"{path} not found: build it with `python -m biped_pympc_amd.build` (hipcc, gfx950). "
             "There is no CPU fallback for the SRBD-MPC kernels.")
+    # torch first: it maps the HIP runtime bundled with it, which libsrbd_mpc.so then shares. Mapped the
+    # other way round (build() and smoke() in one process) the process holds two HIP runtimes and the
+    # library's own finds no device (every launch fails with code 100).
+    import torch  # noqa: F401
     L = ctypes.CDLL(path)
     if os.environ.get("SRBD_LIB"):  # an earlier build (A/B runs): bind what it exports
         L = _Tolerant(L)

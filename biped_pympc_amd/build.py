@@ -206,5 +206,55 @@ def build(force: bool = False, verbose: bool = False) -> str:
     return core
 
 
+# ---- test-only primitive harness (tests/csrc/prim_harness.hip -> tests/libprim_harness.so) ----
+# Not a product source: it lives outside csrc/, so core_sources(), source_hash() and the product
+# libraries do not depend on it. tests/test_gpu_primitives.py loads it with ctypes.
+PRIM_HARNESS_SRC = os.path.join(ROOT, "tests", "csrc", "prim_harness.hip")
+PRIM_HARNESS_LIB = os.path.join(ROOT, "tests", "libprim_harness.so")
+_PRIM_ID_RE = re.compile(rb"srbd-prim-id:([0-9a-f]{16})")
+
+
+def prim_harness_hash() -> str:
+    """Id of the primitive harness: sha256 over the harness source, every csrc/*.hpp it may include
+    and the compile flags. The GPU tests fail when the library's embedded id differs from this."""
+    parts = [ARCH, repr(_COMMON_FLAGS), "prim_harness.hip", open(PRIM_HARNESS_SRC, "rb").read()]
+    for f in sorted(os.listdir(CSRC)):
+        if f.endswith(".hpp"):
+            parts += [f, open(os.path.join(CSRC, f), "rb").read()]
+    return _digest(parts)
+
+
+def prim_harness_embedded_id(path: str = PRIM_HARNESS_LIB) -> str | None:
+    try:
+        with open(path, "rb") as fh:
+            m = _PRIM_ID_RE.search(fh.read())
+    except OSError:
+        return None
+    return m.group(1).decode() if m else None
+
+
+def prim_harness_compile_cmd(extra: list[str]) -> list[str]:
+    """hipcc command line of the harness with the product's architecture and common flags (the ISA
+    audit of tests/test_prim_harness_isa.py appends --cuda-device-only -S)."""
+    return [HIPCC, f"--offload-arch={ARCH}", *_COMMON_FLAGS, f"-I{CSRC}", *extra, PRIM_HARNESS_SRC]
+
+
+def build_prim_harness(force: bool = False, verbose: bool = False) -> str:
+    """Compile the test-only primitive harness in one hipcc call; reused while its embedded id
+    matches prim_harness_hash()."""
+    pid = prim_harness_hash()
+    if force or prim_harness_embedded_id() != pid:
+        tmp = PRIM_HARNESS_LIB + ".tmp"
+        cmd = prim_harness_compile_cmd(["-fPIC", "-shared", f'-DSRBD_PRIM_ID="{pid}"', "-o", tmp])
+        if verbose:
+            print(" ".join(cmd))
+        _run(cmd)
+        os.replace(tmp, PRIM_HARNESS_LIB)
+        if prim_harness_embedded_id() != pid:
+            raise RuntimeError(f"{PRIM_HARNESS_LIB}: id {prim_harness_embedded_id()} != source hash {pid}")
+    return PRIM_HARNESS_LIB
+
+
 if __name__ == "__main__":
     print(build(force=True, verbose=True))
+    print(build_prim_harness(force=True, verbose=True))

@@ -104,6 +104,10 @@ __device__ __forceinline__ double dot_bc12(const double (&c)[12], double v) {
 // zeroed on them right after the broadcast (t = a_kk id = 0 makes their update a no-op), then set
 // to -1 with scale <- id after the update.
 // On exit Dr[j] = (A^-1)_rj.
+// tests/test_gpu_primitives.py runs the sweep alone (test_inverse_rows12_*): both sweeps give the same
+// bits, a block's bits do not depend on its group, on the other group's block or on whether the other
+// group is active, lanes 12..15 repeat lane 11, a diagonal block inverts exactly, and the error stays
+// within 4x that of a plain NumPy restatement up to cond 1e12.
 template <int K>
 struct PivotLanes {  // s_and_saveexec_b64 literal (32-bit, sign-extended; lanes >= 32 are inactive)
   static constexpr uint32_t m16 = (1u << K) | (K == 11 ? 0xF000u : 0u);

@@ -101,10 +101,22 @@ struct RegLayout {
 // 24-bit multiplier: the compiler cannot bound an opaque lane to 24 bits, so it emits the
 // quarter-rate v_mul_lo_u32 / v_mul_hi_u32 for c / 12, 12 i and the like.
 __device__ __forceinline__ int m24(int a, int b) { return (int)__umul24((unsigned)a, (unsigned)b); }
-// c / 12 and c / 6 by reciprocal multiplication: 43691 * 12 = 2^19 + 4, exact for 0 <= c < 2^17
-// (c / 6: < 2^16, where the product also stays below 2^32)
-__device__ __forceinline__ int div12(int c) { return (int)(__umul24((unsigned)c, 43691u) >> 19); }
-__device__ __forceinline__ int div6(int c) { return (int)(__umul24((unsigned)c, 43691u) >> 18); }
+// c / 12 and c / 6 by reciprocal multiplication, each held exhaustively by
+// tests/test_gpu_primitives.py test_div12_div6_exhaustive. c / 12 = (c >> 2) / 3 with 43691 * 3 = 2^17 + 1:
+// exact for 0 <= c < 2^17, where the product stays below 2^31. (c * 43691 >> 19, the form until that
+// test, has the same quotient error bound but its 32-bit product wraps from c = 98304 = 2^32 / 43691 on;
+// the kernels' own arguments, c < 1024, never got there.) c / 6: 43691 * 6 = 2^18 + 2, exact for
+// 0 <= c < 2^16, where the product stays below 2^32 -- by a LOGICAL shift: HIP declares __umul24 to
+// return int, and the arithmetic shift of a product past 2^31 (c > 49152) gave a negative quotient. The
+// shift is an asm instruction so that the compiler learns nothing about the quotient's sign: a plain
+// unsigned shift tells it q >= 0, and the register allocation that follows spills in the N = 6 CCS
+// kernel (tests/test_isa_hazards.py; the same sensitivity as fresh_lane()'s note on l >= 0).
+__device__ __forceinline__ int div12(int c) { return (int)(__umul24((unsigned)c >> 2, 43691u) >> 17); }
+__device__ __forceinline__ int div6(int c) {
+  int q;
+  asm("v_lshrrev_b32 %0, 18, %1" : "=v"(q) : "v"(__umul24((unsigned)c, 43691u)));
+  return q;
+}
 
 // foot of u column j ({0,1,2,7} left, {3,4,5,10} right, else -1), its position, and the inverse
 __device__ __forceinline__ int foot_of(int j) { return (j < 3 || j == 7) ? 0 : ((j < 6 || j == 10) ? 1 : -1); }

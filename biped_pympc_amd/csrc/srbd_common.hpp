@@ -241,7 +241,10 @@ __host__ __device__ inline int a_pidx(const Tables& t, int N, int i, int r) {
 
 // 1/d: v_rcp_f64 (~2^-24 relative) refined by the cubic step y (1 + e + e^2), e = 1 - d y: correctly
 // rounded on 4M log-uniform samples (scripts/microbench_fp64.hip), i.e. the reference's IEEE 1 / d, for
-// three dependent FMAs. Round 6: the Newton step y (1 + e) alone (~2^-46 relative, -DSRBD_RCP_NEWTON),
+// three dependent FMAs. Held by tests/test_gpu_primitives.py test_rcp3_is_correctly_rounded: bit-equal to
+// IEEE 1 / d on 2^22 log-uniform magnitudes in [2^-500, 2^500], the powers of two and 4096 neighbours of 1
+// and of 2, both signs; the 4x4 foot factors' reciprocal slots by
+// test_foot_ldlt_reciprocal_slots_are_correctly_rounded. Round 6: the Newton step y (1 + e) alone (~2^-46 relative, -DSRBD_RCP_NEWTON),
 // the product's choice since round 1 (profiles/r01/rcp_variants.txt: -0.6 % at N = 10, parity magnitudes
 // in the tests unchanged), left the parity campaign's register kernels at 7 / 11 failing cases of 6657
 // per sequence where correctly rounded reciprocals give 3 / 2 -- through the solves' pivots (the 12x12

@@ -15,7 +15,8 @@ import torch
 from biped_pympc_amd import layout, solver
 from biped_pympc_amd.utils.synthetic import make_workload, solver_init
 from oracle import oracle
-from tests._util import dense_floor_env, rel_err, rel_err_rows
+from tests._util import (SWEEP_CASES, SWEEP_HORIZONS, dense_floor_env, rel_err, rel_err_rows,
+                         sweep_solver_inputs)
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
@@ -110,6 +111,34 @@ def test_runtime_horizon_solver_matches_oracle(N, K, path):
     assert np.all(np.isfinite(out[5].cpu().numpy()))  # no fallback sentinel left behind
 
 
+# the register horizons that neither test_solver_matches_oracle (10, 20) nor
+# test_runtime_horizon_solver_matches_oracle (2, 3, 5, 15, 16, 25, 32) runs on "auto" (tests/_util.py)
+assert SWEEP_CASES == [(1, dict(SOLVER_CASES)[1]), (3, dict(SOLVER_CASES)[5])]
+
+
+@pytest.mark.parametrize("K,tol", SWEEP_CASES)
+@pytest.mark.parametrize("N", SWEEP_HORIZONS)
+def test_every_register_horizon_solver_matches_oracle(N, K, tol):
+    """The register kernels are 31 separately scheduled template instances (N = 2..32); this runs the
+    22 the two tests above leave out, on "auto" (the register kernel), B = 16 randomized-gait envs, per
+    env against oracle.pdipm at the K = 1 tolerance of SOLVER_CASES for K = 1 and its K = 5 tolerance for
+    K = 3. Seed rule: seed = 700 + N + 100 j for the first j >= 0 at which every env's floor between the two
+    CPU restatements (tests/_util.py dense_floor_env: the oracle vs oracle/pdipm_dense.py) is at most a
+    quarter of the tolerance at both K -- so the tolerance is never the floor's. The rule is held on the
+    CPU by tests/test_sweep_floor.py on these very inputs (tests/_util.py sweep_solver_inputs): j = 0 at
+    all 22 horizons; worst floors 1.4e-11 (K = 1, N = 30) and 1.6e-10 (K = 3, N = 31)."""
+    ins = sweep_solver_inputs(N)
+    ref = oracle.pdipm(N, K, ins)
+    out = solver.pdipm(_cuda(ins[:6]), _cuda(ins[6:]), N, K)
+    torch.cuda.synchronize()
+    for k, v in enumerate("xszy"):
+        o = out[k].cpu().numpy()
+        assert np.all(np.isfinite(o)), (N, K, v)
+        err = rel_err_rows(o, ref[k])
+        assert np.all(err <= tol), (N, K, v, err.max())
+    assert np.all(np.isfinite(out[5].cpu().numpy()))  # no fallback sentinel left behind
+
+
 @pytest.mark.parametrize("path", ["auto", "lds", "general"])
 @pytest.mark.parametrize("K", [5, 20])
 @pytest.mark.parametrize("N", [1, 10, 20, 32])
@@ -186,6 +215,25 @@ def test_fused_step_equals_former_plus_solver(N, random_gait):
     step kernel, mpc_step_lds.hpp, at N = 1)."""
     B, K = 200, 10
     wl = make_workload(B, N, seed=900 + N, random_gait=random_gait, residuals=random_gait)
+    ins = _cuda(wl.inputs)
+    fused = [t.clone() for t in solver.mpc_solve(ins, N, K, fused=True)]
+    plain = solver.mpc_solve(ins, N, K, fused=False)
+    torch.cuda.synchronize()
+    for a, c in zip(fused, plain):
+        assert torch.equal(a, c)
+
+
+FUSED_LISTED = (10, 20, 5, 1, 3, 16, 9, 32, 11, 15, 21, 25)  # test_fused_step_equals_former_plus_solver
+
+
+@pytest.mark.parametrize("N", [N for N in range(1, 33) if N not in FUSED_LISTED])
+def test_fused_step_equals_former_plus_solver_every_other_horizon(N):
+    """The same bit-for-bit check at the 20 horizons the test above does not list (each register
+    horizon has its own fused and CCS kernel instance), small: B = 8, K = 2; randomized gait and
+    residual outputs at the even horizons, the standing gait at the odd ones."""
+    B, K = 8, 2
+    rg = N % 2 == 0
+    wl = make_workload(B, N, seed=900 + N, random_gait=rg, residuals=rg)
     ins = _cuda(wl.inputs)
     fused = [t.clone() for t in solver.mpc_solve(ins, N, K, fused=True)]
     plain = solver.mpc_solve(ins, N, K, fused=False)
@@ -802,3 +850,18 @@ def test_solver_call_captured_in_a_hip_graph():
     torch.cuda.synchronize()
     for k in range(6):
         assert torch.equal(out[k], eager[k]), k
+
+
+def test_library_bound_before_torch_still_finds_the_device():
+    """A fresh process that binds libsrbd_mpc.so before anything imported torch -- what
+    __graft_entry__.build() followed by smoke() in one process does -- still runs the kernels: _native.lib()
+    maps torch's bundled HIP runtime first. Mapped the other way round, the process held two runtimes and
+    every launch of the library failed with HIP error 100 (no device). This test is about the process's
+    load order, hence the one child process."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import sys; from biped_pympc_amd import _native; assert 'torch' not in sys.modules; "
+            "assert _native.lib().srbd_abi_version() == 1; import __graft_entry__ as g; g.smoke()")
+    r = subprocess.run([sys.executable, "-c", code], cwd=root, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "smoke ok" in r.stdout, (r.stdout[-500:], r.stderr[-1500:])
