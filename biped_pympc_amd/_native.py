@@ -69,6 +69,12 @@ def lib() -> ctypes.CDLL:
     L.srbd_pdipm_ex.restype = ctypes.c_int
     L.srbd_pdipm_ex.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, P, P,
                                 _c_dp, ctypes.c_void_p]
+    # the *_info entry points: srbd_solve_info* in place of the status pointer
+    IP = ctypes.POINTER(SolveInfo)
+    L.srbd_pdipm_info.restype = ctypes.c_int
+    L.srbd_pdipm_info.argtypes = L.srbd_pdipm_ex.argtypes[:-2] + [IP, ctypes.c_void_p]
+    L.srbd_mpc_solve_fused_info.restype = ctypes.c_int
+    L.srbd_mpc_solve_fused_info.argtypes = L.srbd_mpc_solve_fused_ex.argtypes[:-2] + [IP, ctypes.c_void_p]
     L.srbd_prepare_device.restype = ctypes.c_int
     L.srbd_prepare_device.argtypes = []
     L.srbd_release_device.restype = ctypes.c_int
@@ -107,6 +113,8 @@ def lib() -> ctypes.CDLL:
                                 P, P, _c_dp, ctypes.c_int, _c_dp, _c_dp, _c_dp, ctypes.c_void_p]
     L.srbd_mpc_step_ex.restype = ctypes.c_int
     L.srbd_mpc_step_ex.argtypes = L.srbd_mpc_step.argtypes[:-1] + [_c_dp, ctypes.c_void_p]
+    L.srbd_mpc_step_info.restype = ctypes.c_int
+    L.srbd_mpc_step_info.argtypes = L.srbd_mpc_step.argtypes[:-1] + [IP, ctypes.c_void_p]
     L.srbd_u0_wrench.restype = ctypes.c_int
     L.srbd_u0_wrench.argtypes = [ctypes.c_int, ctypes.c_int, _c_dp, _c_dp, _c_dp, ctypes.c_void_p]
     L.srbd_u0_wrench_torque.restype = ctypes.c_int
@@ -152,6 +160,19 @@ class MPCPrep(ctypes.Structure):
         ("I_body", ctypes.c_float * 9), ("mass", ctypes.c_double), ("mu", ctypes.c_double),
         ("Q", ctypes.c_float * 13), ("q_len", ctypes.c_int), ("R", ctypes.c_float * 12),
         ("step_dt", ctypes.c_float), ("literal_layout", ctypes.c_int)]
+
+
+class SolveInfo(ctypes.Structure):
+    """ctypes mirror of ``srbd_solve_info`` (include/srbd_mpc.h): the per-problem extras of a solve,
+    device pointers as void* (None: not computed)."""
+    _fields_ = [("status", _c_dp), ("objective", _c_dp), ("objective_f32", _c_dp)]
+
+
+def solve_info(status=None, objective=None, objective_f32=None):
+    """A ``SolveInfo`` of the given device pointers, or None when all are None (the plain entry points)."""
+    if status is None and objective is None and objective_f32 is None:
+        return None
+    return SolveInfo(status, objective, objective_f32)
 
 
 def ptr_array(ptrs) -> ctypes.Array:

@@ -57,6 +57,8 @@ class MPCConf:
     literal_layout: bool = True
     keep_solution: bool = False  # also write the QP solution (x, s, z, y, residuals, mu) to .solution
     #                              and the 17 prepared former inputs to .former_inputs
+    compute_cost: bool = False   # fill run()'s cost with the QP objective 0.5 x^T H x + f^T x of the solution
+    #                              (the reference's MPCController.mpc_cost; its CusADi back end returns zeros)
 
 
 @dataclass
@@ -183,6 +185,9 @@ class MPCControllerHIP(BaseMPCController):
         self.former_inputs = [torch.empty((B, w), dtype=torch.float64, device=dev) for w in d.former_in_nnz]
         self.buffers = solver.MPCSolveBuffers.allocate(N, B, dev)
         self.foot_wrench = torch.empty((B, 2, 6), dtype=torch.float32, device=dev)
+        # the MPC cost run() returns: zeros (the reference's CusADi back end), or with cfg.compute_cost
+        # the QP objective of the step's solution, written by the solver kernel; allocated once, so a
+        # captured graph keeps writing this storage (a step with compute_cost off does not touch it)
         self.cost = torch.zeros(B, device=dev)
         self.tau = None  # (B, 2, ndof) float32, allocated by run_with_torque
         # per-env status word of the last step (include/srbd_mpc.h SRBD_STATUS_*: 1 non-finite
@@ -265,16 +270,23 @@ class MPCControllerHIP(BaseMPCController):
         args = (N, self.cfg.pdipm_iterations, B, float(self.cfg.y0), ctypes.byref(p), fin, outs,
                 self.foot_wrench.data_ptr(), 0 if J is None else J.shape[3], None if J is None else J.data_ptr(),
                 None if cb is None else cb.data_ptr(), None if J is None else self.tau.data_ptr())
-        if self.status is not None:
-            rc = _native.lib().srbd_mpc_step_ex(*args, solver._check_status(self.status, B, "MPCControllerHIP.status"),
-                                                solver._stream_ptr())
+        st = solver._check_status(self.status, B, "MPCControllerHIP.status")
+        if self.cfg.compute_cost:
+            rc = _native.lib().srbd_mpc_step_info(*args, _native.solve_info(st, None, self._cost_ptr()),
+                                                  solver._stream_ptr())
+        elif st is not None:
+            rc = _native.lib().srbd_mpc_step_ex(*args, st, solver._stream_ptr())
         else:
             rc = _native.lib().srbd_mpc_step(*args, solver._stream_ptr())
         _native.check(rc, "srbd_mpc_step")
         self.solution = self.buffers.outputs if self.cfg.keep_solution else None
 
+    def _cost_ptr(self) -> int:
+        return solver._check_objective(self.cost, self.num_envs, "MPCControllerHIP.cost", torch.float32, "cost")
+
     def run(self) -> Tuple[torch.Tensor, torch.Tensor]:
-        """MPCControllerCusadi.run (mpc_controller_cusadi.py:43-205): (foot_wrench (B,2,6) f32, cost)."""
+        """MPCControllerCusadi.run (mpc_controller_cusadi.py:43-205): (foot_wrench (B,2,6) f32, cost);
+        cost (B,) float32 is the QP objective of the solution with cfg.compute_cost, zeros otherwise."""
         keep: list = []
         self._step(self._prep_struct(keep), None, None)
         return self.foot_wrench, self.cost
@@ -285,7 +297,8 @@ class MPCControllerHIP(BaseMPCController):
         Bit-identical to run() (tests/test_controller.py)."""
         N, B = self.horizon_length, self.num_envs
         self.prepare()
-        out = solver.mpc_solve(self.former_inputs, N, self.cfg.pdipm_iterations, self.cfg.y0, self.buffers)
+        out = solver.mpc_solve(self.former_inputs, N, self.cfg.pdipm_iterations, self.cfg.y0, self.buffers,
+                               objective_f32=self.cost if self.cfg.compute_cost else None)
         self.solution = out if self.cfg.keep_solution else None  # as run(): exposed on request only
         rot = _f32(self.state_estimate_data.rotation_body, self.device)
         rc = _native.lib().srbd_u0_wrench_torque(
@@ -333,7 +346,8 @@ class GraphedMPCStep:
     between replays. Every replay first compares the storage of every source tensor -- the state
     estimate and command fields, the contact schedule, dt_mpc, the residual accelerations, the
     knot-point state -- with what was captured, and the constants baked into the graph (mass, mu,
-    I_body, Q, R, step dt, layout, iterations, y0, the device's refinement mode of srbd_set_refinement):
+    I_body, Q, R, step dt, layout, iterations, y0, compute_cost and the cost tensor's storage, the
+    device's refinement mode of srbd_set_refinement):
     a tensor replaced by assignment
     (``data.root_position = ...``, ``c.residual_lin_accel = x.clone()``, a setter) or a changed
     constant makes the replay raise instead of silently reading the captured values. (Q and R given
@@ -385,7 +399,8 @@ class GraphedMPCStep:
         consts = (("mass", c.mass), ("mu", c.mu), ("I_body", value(c.I_body)), ("Q", value(c.Q)),
                   ("R", value(c.R)), ("step_dt", c.cfg.decimation * c.cfg.dt),
                   ("literal_layout", c.cfg.literal_layout), ("pdipm_iterations", c.cfg.pdipm_iterations),
-                  ("y0", c.cfg.y0), ("keep_solution", c.cfg.keep_solution),
+                  ("y0", c.cfg.y0), ("keep_solution", c.cfg.keep_solution), ("compute_cost", c.cfg.compute_cost),
+                  ("cost", c.cost.data_ptr()),
                   ("refinement", _native.current_refinement()))  # baked into the kernel's arguments
         return tuple((n, t.data_ptr()) for n, t in src) + consts
 

@@ -111,6 +111,10 @@ __global__ __launch_bounds__(64) void mpc_step_lds_kernel(FusedArgs fa) {
     const int st = C.status(res[3], floor_hit);
     if (lane == 0) fa.status[env] = st;
   }
+  if (fa.objective || fa.objective_f32) {
+    const double J = C.objective();
+    if (lane == 0) objective_store(J, env, fa.objective, fa.objective_f32);
+  }
   // ---- outputs (each optional) ----
   if (double* xo = fa.out[0])
     for (int e = lane; e < nz; e += 64) xo[(size_t)env * nz + e] = C.X[e];

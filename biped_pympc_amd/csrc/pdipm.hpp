@@ -51,6 +51,8 @@ struct SolverArgs {
   int* status;  // (batch) per-problem status word (kStatus* bits), or null: not written
   int refine_policy;  // the register kernels' refinement policy word (srbd_set_refinement_policy)
   double refine_w;    // its W = z / s vote threshold (INFINITY: no W vote)
+  double* objective;     // (batch) the QP objective J of the returned x (objective_acc), or null
+  float* objective_f32;  // (batch) the same J rounded once to FP32, or null
 };
 
 // Refinement policy word of the register kernels (include/srbd_mpc.h SRBD_REFINE_*): bit 0 the affine
@@ -65,6 +67,24 @@ constexpr int kRefineAffineAll = 1, kRefineAffineAtInit = 2;
 constexpr int kStatusNonFinite = 1, kStatusStepFloor = 2, kStatusFallback = 4;
 constexpr int kLockStride = 32;  // ints between two slots' lock words
 __device__ __forceinline__ bool not_finite(double v) { return !__builtin_isfinite(v); }
+
+// The QP objective of the returned iterate, J = sum_e (H_e x_e / 2 + f_e) x_e over the 24N primal
+// entries (H is diagonal in its CCS pattern): the reference's 0.5 x^T H x + f^T x
+// (mpc_controller_qpth.py:136; OSQP's obj_val), without the constant x_ref^T Q x_ref / 2. Every solver
+// kernel forms it in its epilogue when asked (SolverArgs / FusedArgs objective, objective_f32): each
+// lane adds the terms of the entries it owns with objective_acc -- two roundings per term (the FMA and
+// the product; H_e / 2 is exact) and one per addition, never contracted, so two kernels that add the
+// same terms in the same order return the same bits -- one team reduction follows, lane 0 stores.
+// A non-finite x propagates into J (the status word reports it).
+__device__ __forceinline__ double objective_acc(double acc, double h, double f, double x) {
+#pragma clang fp contract(off)
+  const double t = fma(0.5 * h, x, f);
+  return acc + t * x;
+}
+__device__ __forceinline__ void objective_store(double J, int env, double* o64, float* o32) {
+  if (o64) o64[env] = J;
+  if (o32) o32[env] = (float)J;
+}
 
 // iterative-refinement steps per direction in the LDS-resident and general kernels (the register
 // kernels' one step sits at the FP64 floor at N = 10 / 20)
@@ -1163,6 +1183,12 @@ __device__ __forceinline__ void pdipm_general_at(const SolverArgs& args, int env
     nf = C.team_sum(nf ? 1.0 : 0.0) > 0.0;
     if (lane == 0)
       args.status[env] = status_bits | (nf ? kStatusNonFinite : 0) | (floor_hit ? kStatusStepFloor : 0);
+  }
+  if (args.objective || args.objective_f32) {  // uniform; H per entry (stages may differ here)
+    double a = 0.0;
+    for (int e = lane; e < nz; e += nt) a = objective_acc(a, C.HV[e], C.fg[e], C.X[e]);
+    const double J = C.team_sum(a);
+    if (lane == 0) objective_store(J, env, args.objective, args.objective_f32);
   }
 }
 

@@ -708,6 +708,14 @@ struct FastCtx {
     return (__any(nf) ? kStatusNonFinite : 0) | (floor_hit ? kStatusStepFloor : 0);
   }
 
+  // the QP objective of the returned x (pdipm.hpp objective_acc): H from the stage blocks in Hu
+  __device__ double objective() const {
+    const int N = NT > 0 ? NT : N_, nz = 24 * N;
+    double a = 0.0;
+    for (int e = lane; e < nz; e += 64) a = objective_acc(a, Hu[(e < 12 * N ? 12 : 0) + e % 12], fg[e], X[e]);
+    return wave_sum(a);
+  }
+
   __device__ double step_length(const double* v, const double* dv) const {
     const int N = NT > 0 ? NT : N_, nz = 24 * N, m = 16 * N, p = 14 * N;
     (void)nz; (void)m; (void)p;
@@ -821,6 +829,10 @@ __global__ __launch_bounds__(64) void pdipm_srbd_kernel(SolverArgs args) {
   if (args.status) {
     const int st = C.status(res[3], floor_hit);
     if (lane == 0) args.status[env] = st;
+  }
+  if (args.objective || args.objective_f32) {
+    const double J = C.objective();
+    if (lane == 0) objective_store(J, env, args.objective, args.objective_f32);
   }
 }
 

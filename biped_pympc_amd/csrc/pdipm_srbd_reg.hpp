@@ -615,6 +615,26 @@ struct RegCtx {
     return want_mu ? block_sum(sz) / m : 0.0;
   }
 
+  // The QP objective of the returned x (pdipm.hpp objective_acc) over the x / u columns this lane owns
+  // in r_x (residuals' mapping: f from the owner registers, or re-read where the CCS kernel does not
+  // hold it), H from the stage blocks in Hu; one block reduction. The fused and the CCS kernel share
+  // this method, so both add the same terms in the same order: the same bits.
+  __device__ double objective() {
+    const int lane = fresh_lane();
+    const double *X = at(Lo::X), *Hu = at(Lo::Hu);
+    double a = 0.0;
+#pragma unroll
+    for (int t = 0; t < SX; ++t) {
+      const int c = lane + TPB * t;
+      if (full_slot(t, nx) || c < nx) {
+        const int j = c - m24(div12(c), 12);
+        a = objective_acc(a, Hu[12 + j], (kFReg || t == 0) ? fxr[t] : fg()[c], X[c]);
+        a = objective_acc(a, Hu[j], (kFReg || t == 0) ? fur[t] : fg()[nx + c], X[nx + c]);
+      }
+    }
+    return block_sum(a);
+  }
+
   // Right-hand side of forward elimination step t: g_i - C w_{i-1} (base = this lane's g_i entry),
   // and at the middle step also - C^T v_{mid+1} of group 1 (its lanes compute - C v with base 0
   // and hand it to group 0 through ds_bpermute)
@@ -1320,6 +1340,8 @@ struct FusedArgs {
   int* status;     // (B) per-problem status word (pdipm.hpp kStatus*), or null
   int refine_policy;  // srbd_set_refinement_policy's word (include/srbd_mpc.h SRBD_REFINE_*)
   double refine_w;    // the W = z / s vote's threshold (INFINITY: no W vote)
+  double* objective;     // (B) the QP objective J of the returned x (pdipm.hpp objective_acc), or null
+  float* objective_f32;  // (B) the same J rounded once to FP32, or null
 };
 
 // Body shared by the solver kernel (kFused = false: the QP comes from qp_former's CCS outputs and is
@@ -1799,6 +1821,11 @@ __device__ __forceinline__ void reg_kernel_body(const SolverArgs& args, const Fu
       if (RegCtx<N>::full_slot(t, m) || ul + TPB * t < m) nf = nf || not_finite(C.s[t]) || not_finite(C.z[t]);
     nf = C.block_any(nf);
     if (lane == 0) st[env] = (nf ? kStatusNonFinite : 0) | (SG[15] != 0.0 ? kStatusStepFloor : 0);
+  }
+  if ((kFused ? fa.objective : args.objective) || (kFused ? fa.objective_f32 : args.objective_f32)) {  // uniform
+    const double J = C.objective();
+    if (lane == 0)
+      objective_store(J, env, kFused ? fa.objective : args.objective, kFused ? fa.objective_f32 : args.objective_f32);
   }
   if constexpr (kFused) {
     if (fa.wrench) {  // u0 -> foot wrench (+ stance torque): srbd_u0_wrench_torque's arithmetic

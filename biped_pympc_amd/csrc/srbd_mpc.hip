@@ -106,6 +106,16 @@ void set_refinement_args(Args& a) {
   a.refine_w = w > 0.0 ? w : INFINITY;
 }
 
+// the per-problem extras of a call (srbd_solve_info, any of them or the struct itself null) into the
+// kernel arguments
+template <class Args>
+void set_info_args(Args& a, const srbd_solve_info* info) {
+  a.status = info ? info->status : nullptr;
+  a.objective = info ? info->objective : nullptr;
+  a.objective_f32 = info ? info->objective_f32 : nullptr;
+}
+srbd_solve_info status_only(int* status) { return srbd_solve_info{status, nullptr, nullptr}; }
+
 int ensure_lds_attr(const void* fn, size_t bytes, srbd::LdsAttr& cache) {
   const int dev = current_device();
   if (dev < 0) return set_error((int)hipErrorInvalidDevice, "no current HIP device (or index >= 64)");
@@ -467,8 +477,8 @@ int srbd_qp_former(int horizon, int batch, const double* const* inputs, double* 
   return launch_former(a, (hipStream_t)stream);
 }
 
-static int pdipm_common(int horizon, int n_iter, int batch, double y0, int init_mode,
-                        const double* const* inputs, double* const* outputs, int* status, void* stream) {
+static int pdipm_common(int horizon, int n_iter, int batch, double y0, int init_mode, const double* const* inputs,
+                        double* const* outputs, const srbd_solve_info* info, void* stream) {
   if (!horizon_ok(horizon) || n_iter < 1 || batch < 0 || !inputs || !outputs)
     return set_error(kErrInvalid, "srbd_pdipm: bad arguments");
   if (batch == 0) return 0;
@@ -487,7 +497,7 @@ static int pdipm_common(int horizon, int n_iter, int batch, double y0, int init_
   a.batch = batch;
   a.init_mode = init_mode;
   a.y0 = y0;
-  a.status = status;
+  set_info_args(a, info);
   return launch_solver(a, (hipStream_t)stream);
 }
 
@@ -507,16 +517,23 @@ int srbd_pdipm_ccs(int horizon, int n_iter, int batch, const double* const* inpu
   return pdipm_common(horizon, n_iter, batch, 0.0, 2, inputs, outputs, nullptr, stream);
 }
 
+int srbd_pdipm_info(int horizon, int n_iter, int batch, int init_mode, double y0, const double* const* inputs,
+                    double* const* outputs, const srbd_solve_info* info, void* stream) {
+  if (init_mode < 0 || init_mode > 2) return set_error(kErrInvalid, "srbd_pdipm_info: init_mode 0, 1 or 2");
+  if (init_mode == 2 && (!inputs || (batch > 0 && !inputs[6])))
+    return set_error(kErrInvalid, "srbd_pdipm_info: null x_init");
+  return pdipm_common(horizon, n_iter, batch, init_mode == 1 ? y0 : 0.0, init_mode, inputs, outputs, info, stream);
+}
+
 int srbd_pdipm_ex(int horizon, int n_iter, int batch, int init_mode, double y0, const double* const* inputs,
                   double* const* outputs, int* status, void* stream) {
-  if (init_mode < 0 || init_mode > 2) return set_error(kErrInvalid, "srbd_pdipm_ex: init_mode 0, 1 or 2");
-  if (init_mode == 2 && (!inputs || (batch > 0 && !inputs[6])))
-    return set_error(kErrInvalid, "srbd_pdipm_ex: null x_init");
-  return pdipm_common(horizon, n_iter, batch, init_mode == 1 ? y0 : 0.0, init_mode, inputs, outputs, status, stream);
+  const srbd_solve_info info = status_only(status);
+  return srbd_pdipm_info(horizon, n_iter, batch, init_mode, y0, inputs, outputs, &info, stream);
 }
 
 static int mpc_solve_two_kernels(int horizon, int n_iter, int batch, double y0, const double* const* former_inputs,
-                                 double* qp_workspace, double* const* outputs, int* status, void* stream) {
+                                 double* qp_workspace, double* const* outputs, const srbd_solve_info* info,
+                                 void* stream) {
   if (!horizon_ok(horizon) || !qp_workspace) return set_error(kErrInvalid, "srbd_mpc_solve: bad arguments");
   const size_t N = (size_t)horizon, B = (size_t)(batch < 0 ? 0 : batch);
   double* H = qp_workspace;
@@ -528,7 +545,7 @@ static int mpc_solve_two_kernels(int horizon, int n_iter, int batch, double y0, 
   double* qp[6] = {H, f, A, b, G, d};
   if (int rc = srbd_qp_former(horizon, batch, former_inputs, qp, stream)) return rc;
   const double* sin[10] = {H, G, A, f, d, b, nullptr, nullptr, nullptr, nullptr};
-  return pdipm_common(horizon, n_iter, batch, y0, 1, sin, outputs, status, stream);
+  return pdipm_common(horizon, n_iter, batch, y0, 1, sin, outputs, info, stream);
 }
 
 int srbd_mpc_solve(int horizon, int n_iter, int batch, double y0, const double* const* former_inputs,
@@ -563,12 +580,13 @@ static int launch_step(const srbd::FusedArgs& a0, hipStream_t st) {
   return e == hipSuccess ? 0 : set_error((int)e, "mpc_step_reg_kernel launch");
 }
 
-int srbd_mpc_solve_fused_ex(int horizon, int n_iter, int batch, double y0, const double* const* former_inputs,
-                            double* qp_workspace, double* const* outputs, int* status, void* stream) {
+int srbd_mpc_solve_fused_info(int horizon, int n_iter, int batch, double y0, const double* const* former_inputs,
+                              double* qp_workspace, double* const* outputs, const srbd_solve_info* info,
+                              void* stream) {
   if (!horizon_ok(horizon)) return set_error(kErrInvalid, "srbd_mpc_solve_fused: bad horizon");
   if (solver_path() != 0) {  // a non-auto solver path: former + that solver kernel
     if (!qp_workspace) return set_error(kErrInvalid, "srbd_mpc_solve_fused: a non-auto solver path needs qp_workspace");
-    return mpc_solve_two_kernels(horizon, n_iter, batch, y0, former_inputs, qp_workspace, outputs, status, stream);
+    return mpc_solve_two_kernels(horizon, n_iter, batch, y0, former_inputs, qp_workspace, outputs, info, stream);
   }
   if (n_iter < 1 || batch < 0 || !former_inputs || !outputs)
     return set_error(kErrInvalid, "srbd_mpc_solve_fused: bad arguments");
@@ -589,8 +607,14 @@ int srbd_mpc_solve_fused_ex(int horizon, int n_iter, int batch, double y0, const
   a.n_iter = n_iter;
   a.batch = batch;
   a.y0 = y0;
-  a.status = status;
+  set_info_args(a, info);
   return launch_step(a, (hipStream_t)stream);
+}
+
+int srbd_mpc_solve_fused_ex(int horizon, int n_iter, int batch, double y0, const double* const* former_inputs,
+                            double* qp_workspace, double* const* outputs, int* status, void* stream) {
+  const srbd_solve_info info = status_only(status);
+  return srbd_mpc_solve_fused_info(horizon, n_iter, batch, y0, former_inputs, qp_workspace, outputs, &info, stream);
 }
 
 int srbd_mpc_solve_fused(int horizon, int n_iter, int batch, double y0, const double* const* former_inputs,
@@ -639,10 +663,10 @@ static int fill_prep(const srbd_mpc_prep* p, srbd::PrepArgs& a, const char* who)
   return 0;
 }
 
-int srbd_mpc_step_ex(int horizon, int n_iter, int batch, double y0, const srbd_mpc_prep* prep,
-                     double* const* former_inputs, double* const* outputs, float* foot_wrench, int ndof,
-                     const float* contact_jacobian, const float* contact_bool, float* tau, int* status,
-                     void* stream) {
+int srbd_mpc_step_info(int horizon, int n_iter, int batch, double y0, const srbd_mpc_prep* prep,
+                       double* const* former_inputs, double* const* outputs, float* foot_wrench, int ndof,
+                       const float* contact_jacobian, const float* contact_bool, float* tau,
+                       const srbd_solve_info* info, void* stream) {
   if (!horizon_ok(horizon)) return set_error(kErrInvalid, "srbd_mpc_step: bad horizon");
   if (n_iter < 1 || batch < 0 || !prep || (tau && (ndof < 1 || ndof > 64)))
     return set_error(kErrInvalid, "srbd_mpc_step: bad arguments");
@@ -670,8 +694,17 @@ int srbd_mpc_step_ex(int horizon, int n_iter, int batch, double y0, const srbd_m
   a.n_iter = n_iter;
   a.batch = batch;
   a.y0 = y0;
-  a.status = status;
+  set_info_args(a, info);
   return launch_step(a, (hipStream_t)stream);
+}
+
+int srbd_mpc_step_ex(int horizon, int n_iter, int batch, double y0, const srbd_mpc_prep* prep,
+                     double* const* former_inputs, double* const* outputs, float* foot_wrench, int ndof,
+                     const float* contact_jacobian, const float* contact_bool, float* tau, int* status,
+                     void* stream) {
+  const srbd_solve_info info = status_only(status);
+  return srbd_mpc_step_info(horizon, n_iter, batch, y0, prep, former_inputs, outputs, foot_wrench, ndof,
+                            contact_jacobian, contact_bool, tau, &info, stream);
 }
 
 int srbd_mpc_step(int horizon, int n_iter, int batch, double y0, const srbd_mpc_prep* prep,

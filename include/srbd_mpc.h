@@ -85,7 +85,7 @@ int srbd_pdipm_ccs(int horizon, int n_iter, int batch, const double* const* inpu
  *                          "auto" or "lds") solved it by its in-launch general fallback; set only there:
  *                          under the "general" path (srbd_set_solver_path(1)) every QP takes the general
  *                          kernel and this bit stays clear
- * Written by the *_ex entry points when status != NULL (device memory, batch ints). */
+ * Written by the *_ex and *_info entry points when status != NULL (device memory, batch ints). */
 #define SRBD_STATUS_NONFINITE 1
 #define SRBD_STATUS_STEP_FLOOR 2
 #define SRBD_STATUS_FALLBACK 4
@@ -93,6 +93,30 @@ int srbd_pdipm_ccs(int horizon, int n_iter, int batch, const double* const* inpu
 /* srbd_pdipm (init_mode 0), srbd_pdipm_cold (1, y = y0) or srbd_pdipm_ccs (2) with the status word. */
 int srbd_pdipm_ex(int horizon, int n_iter, int batch, int init_mode, double y0, const double* const* inputs,
                   double* const* outputs, int* status, void* stream);
+
+/* Per-problem extras of a solve, each optional (NULL: not computed), all DEVICE memory of `batch`
+ * entries; the *_info entry points take a pointer to this struct (NULL: no extras) where the *_ex ones
+ * take `int* status`. The struct is read during the call only.
+ *   objective: the QP objective of the iterate the call returns (after the last update and clamps),
+ *     J = sum_e (H_e x_e / 2 + f_e) x_e over the 24N primal entries (H's CCS pattern is its diagonal;
+ *     per-stage values are honoured for QPs that are not stage-invariant) = 0.5 x^T H x + f^T x, what
+ *     the reference's qpth and OSQP back ends return as `cost` (mpc_controller_qpth.py:136,
+ *     mpc_controller_osqp.py:95; its CusADi back end returns zeros, mpc_controller_cusadi.py:185) and
+ *     MPCController.mpc_cost exposes (mpc_wrapper.py:151-153). The constant x_ref^T Q x_ref / 2 is not
+ *     added (the reference does not add it). Formed in the solver kernel's epilogue from x, diag(H) and f
+ *     on chip: each term with two roundings, one block sum in a fixed order (the fused step and
+ *     qp_former -> solver give the same bits). A NaN / Inf in x propagates into J; SRBD_STATUS_NONFINITE
+ *     reports it.
+ *   objective_f32: the same J rounded once to FP32 (the dtype of the controller's `cost`). */
+typedef struct srbd_solve_info {
+  int*    status;         /* (B) int32, SRBD_STATUS_* word, or NULL */
+  double* objective;      /* (B) FP64 J, or NULL */
+  float*  objective_f32;  /* (B) the same J rounded once to FP32, or NULL */
+} srbd_solve_info;
+
+/* srbd_pdipm_ex with the extras struct in place of the status pointer (init_mode 0, 1 or 2). */
+int srbd_pdipm_info(int horizon, int n_iter, int batch, int init_mode, double y0, const double* const* inputs,
+                    double* const* outputs, const srbd_solve_info* info, void* stream);
 
 /* Whole MPC QP step: qp_former -> cold-start PDIPM (n_iter iterations), one stream, no host sync.
  * `qp_workspace` is caller-owned device memory of srbd_mpc_workspace_doubles(horizon, batch)
@@ -112,6 +136,11 @@ int srbd_mpc_solve_fused(int horizon, int n_iter, int batch, double y0, const do
 /* srbd_mpc_solve_fused with the status word (status may be NULL). */
 int srbd_mpc_solve_fused_ex(int horizon, int n_iter, int batch, double y0, const double* const* former_inputs,
                             double* qp_workspace, double* const* outputs, int* status, void* stream);
+/* srbd_mpc_solve_fused with the extras struct (info may be NULL); a non-auto solver path runs
+ * former + solver with the same extras. */
+int srbd_mpc_solve_fused_info(int horizon, int n_iter, int batch, double y0, const double* const* former_inputs,
+                              double* qp_workspace, double* const* outputs, const srbd_solve_info* info,
+                              void* stream);
 
 /* LDS bytes one solver workgroup (one QP) uses at this horizon (0 if unsupported). */
 size_t srbd_solver_lds_bytes(int horizon);
@@ -267,6 +296,12 @@ int srbd_mpc_step_ex(int horizon, int n_iter, int batch, double y0, const srbd_m
                      double* const* former_inputs, double* const* outputs, float* foot_wrench, int ndof,
                      const float* contact_jacobian, const float* contact_bool, float* tau, int* status,
                      void* stream);
+/* srbd_mpc_step with the extras struct (info may be NULL): with objective_f32 the step writes the MPC
+ * cost next to the wrench, 4 more bytes per env. */
+int srbd_mpc_step_info(int horizon, int n_iter, int batch, double y0, const srbd_mpc_prep* prep,
+                       double* const* former_inputs, double* const* outputs, float* foot_wrench, int ndof,
+                       const float* contact_jacobian, const float* contact_bool, float* tau,
+                       const srbd_solve_info* info, void* stream);
 
 /* u0 = x[:, 12N:12N+12] -> foot wrench (B,2,6) float32 in the body frame, x-moments zeroed and
  * negated as mpc_controller_cusadi.py:186-203. rotation_body (B,3,3) float32 row-major. */
