@@ -123,6 +123,15 @@ def lib() -> ctypes.CDLL:
     L.srbd_dense_scatter.restype = ctypes.c_int
     L.srbd_dense_scatter.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp, _c_dp,
                                      ctypes.c_void_p]
+    # the backward pass (adjoint KKT solve, former VJP)
+    L.srbd_pdipm_backward.restype = ctypes.c_int
+    L.srbd_pdipm_backward.argtypes = [ctypes.c_int, ctypes.c_int, P, _c_dp, P, _c_dp, ctypes.c_void_p]
+    L.srbd_qp_former_backward.restype = ctypes.c_int
+    L.srbd_qp_former_backward.argtypes = [ctypes.c_int, ctypes.c_int, P, P, P, ctypes.c_void_p]
+    L.srbd_mpc_backward_workspace_doubles.restype = ctypes.c_size_t
+    L.srbd_mpc_backward_workspace_doubles.argtypes = [ctypes.c_int, ctypes.c_int]
+    L.srbd_mpc_backward.restype = ctypes.c_int
+    L.srbd_mpc_backward.argtypes = [ctypes.c_int, ctypes.c_int, P, P, _c_dp, _c_dp, P, _c_dp, ctypes.c_void_p]
     _lib = L
     return L
 
@@ -190,6 +199,7 @@ SOLVER_PATHS = {"auto": 0, "general": 1, "lds": 2}
 
 # per-problem status word bits (include/srbd_mpc.h SRBD_STATUS_*)
 STATUS_NONFINITE, STATUS_STEP_FLOOR, STATUS_FALLBACK = 1, 2, 4
+STATUS_UNSUPPORTED = 8  # backward pass: the QP is not stage-invariant, its gradients are NaN
 
 
 def current_solver_path() -> int:

@@ -125,12 +125,13 @@ def build_dropin(kind: str, N: int, K: int | None) -> str:
     return _build_dropin_lib(fn, N, K, core, False, False)
 
 
-# the two HIP translation units of libsrbd_mpc.so and their unit-specific flags: the N = 20 register
+# the HIP translation units of libsrbd_mpc.so and their unit-specific flags: the N = 20 register
 # kernels in their own unit, scheduled with the register-pressure trackers (csrc/reg20.hpp)
 HIP_UNITS = {
     "srbd_mpc.hip": ["-DSRBD_SPLIT_REG20"],
     "srbd_reg20.hip": ["-mllvm", "-amdgpu-use-amdgpu-trackers=1"],
     "srbd_regN.hip": ["-mllvm", "-amdgpu-use-amdgpu-trackers=1"],  # the other register horizons
+    "srbd_backward.hip": [],  # the backward pass: adjoint KKT solve, QP-data gradients, former VJP
 }
 
 

@@ -364,12 +364,14 @@ struct FastCtx {
   // correction's own Lambda G c_x: re-formed from the whole dx, dz = VV + Lambda G dx rounds G dx at
   // eps |G| |dx| and multiplies that by Lambda = W / (1 + delta W), which at z / s = 6e5 left dz 1e-9
   // off the exact answer after the refinement, scripts/extended_precision_check.py; the correction of
-  // the u columns goes to VV, dead after refine_rhs)
+  // the u columns goes to VV, dead after refine_rhs);
+  // mode 3: the right-hand sides as the caller left them in RX, RS, RE, R2 and VV = D^-1 (r2 + W r_s)
+  // (the adjoint solve of pdipm_backward.hpp: RX = -g, the rest zero), otherwise as mode 0
   __device__ void solve(int mode, double smu) {
     const int N = NT > 0 ? NT : N_, nz = 24 * N, m = 16 * N, p = 14 * N;
     (void)nz; (void)m; (void)p;
     const bool ref = mode == 2;
-    if (!ref) {
+    if (mode < 2) {
       for (int q = lane; q < m; q += 64) {
         const double si = 1.0 / S[q];
         double r2 = -(si * (S[q] * Z[q]));

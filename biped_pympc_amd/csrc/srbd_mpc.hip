@@ -24,6 +24,10 @@
 #include "reg20.hpp"
 #include "regN.hpp"
 #include "device_state.hpp"
+#include "pdipm_backward.hpp"      // BackwardArgs; the kernels are instantiated in srbd_backward.hip
+#include "qp_former_backward.hpp"  // FormerBackwardArgs
+
+static_assert(srbd::kStatusUnsupported == SRBD_STATUS_UNSUPPORTED, "status bits of the header and the kernels");
 
 #ifndef SRBD_BUILD_ID
 #define SRBD_BUILD_ID "0000000000000000"  // diagnostic builds outside biped_pympc_amd/build.py
@@ -712,6 +716,79 @@ int srbd_mpc_step(int horizon, int n_iter, int batch, double y0, const srbd_mpc_
                   const float* contact_jacobian, const float* contact_bool, float* tau, void* stream) {
   return srbd_mpc_step_ex(horizon, n_iter, batch, y0, prep, former_inputs, outputs, foot_wrench, ndof,
                           contact_jacobian, contact_bool, tau, nullptr, stream);
+}
+
+// ---- backward pass (pdipm_backward.hpp, qp_former_backward.hpp; kernels in srbd_backward.hip) ----
+
+int srbd_pdipm_backward(int horizon, int batch, const double* const* inputs, const double* grad_x,
+                        double* const* qp_grads, int* status, void* stream) {
+  if (!horizon_ok(horizon) || batch < 0 || !inputs || !qp_grads)
+    return set_error(kErrInvalid, "srbd_pdipm_backward: bad arguments");
+  if (batch == 0) return 0;
+  srbd::BackwardArgs a{};
+  for (int i = 0; i < 10; ++i) {
+    if (!inputs[i] && !(i >= 3 && i <= 5)) return set_error(kErrInvalid, "srbd_pdipm_backward: null input");
+    a.in[i] = inputs[i];  // f, h, b (3..5) are not read
+  }
+  if (!grad_x) return set_error(kErrInvalid, "srbd_pdipm_backward: null grad_x");
+  a.grad_x = grad_x;
+  for (int i = 0; i < 6; ++i) a.out[i] = qp_grads[i];  // null: not written
+  a.status = status;
+  a.N = horizon;
+  a.batch = batch;
+  static srbd::LdsAttr cfg_backward;
+  const size_t lds = srbd::backward_lds_bytes(horizon);
+  if (lds > 160 * 1024) return set_error(kErrInvalid, "horizon too large for the LDS-resident backward solve");
+  if (int rc = ensure_lds_attr(srbd::bwd::adjoint_kernel(), lds, cfg_backward)) return rc;
+  srbd::bwd::launch_adjoint(a, lds, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : set_error((int)e, "pdipm_backward_kernel launch");
+}
+
+int srbd_qp_former_backward(int horizon, int batch, const double* const* former_inputs,
+                            const double* const* qp_grads, double* const* input_grads, void* stream) {
+  if (!horizon_ok(horizon) || batch < 0 || !former_inputs || !qp_grads || !input_grads)
+    return set_error(kErrInvalid, "srbd_qp_former_backward: bad arguments");
+  if (batch == 0) return 0;
+  srbd::FormerBackwardArgs a{};
+  for (int i = 0; i < 17; ++i) {
+    if (!former_inputs[i]) return set_error(kErrInvalid, "srbd_qp_former_backward: null input");
+    a.in[i] = former_inputs[i];
+    a.out[i] = input_grads[i];  // null: not written
+  }
+  for (int i = 0; i < 6; ++i) a.g[i] = qp_grads[i];  // null: a zero gradient
+  a.N = horizon;
+  a.batch = batch;
+  srbd::bwd::launch_former_backward(a, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : set_error((int)e, "qp_former_backward_kernel launch");
+}
+
+size_t srbd_mpc_backward_workspace_doubles(int horizon, int batch) {
+  return 2 * srbd_mpc_workspace_doubles(horizon, batch);  // the QP and its six gradients
+}
+
+int srbd_mpc_backward(int horizon, int batch, const double* const* former_inputs, const double* const* iterate,
+                      const double* grad_x, double* workspace, double* const* input_grads, int* status,
+                      void* stream) {
+  if (!horizon_ok(horizon) || batch < 0 || !former_inputs || !iterate || !input_grads)
+    return set_error(kErrInvalid, "srbd_mpc_backward: bad arguments");
+  if (batch == 0) return 0;
+  if (!workspace || !grad_x || !iterate[0] || !iterate[1] || !iterate[2] || !iterate[3])
+    return set_error(kErrInvalid, "srbd_mpc_backward: null workspace / grad_x / iterate");
+  const size_t N = (size_t)horizon, B = (size_t)batch;
+  const size_t w[6] = {24 * N, 24 * N, 122 * N - 24, 14 * N, 28 * N, 16 * N};  // H, f, A, b, G, d
+  double* qp[6];
+  double* gr[6];
+  double* o = workspace;
+  for (int i = 0; i < 12; ++i) {
+    (i < 6 ? qp[i] : gr[i - 6]) = o;
+    o += B * w[i % 6];
+  }
+  if (int rc = srbd_qp_former(horizon, batch, former_inputs, qp, stream)) return rc;
+  const double* sin[10] = {qp[0], qp[4], qp[2], qp[1], qp[5], qp[3], iterate[0], iterate[1], iterate[2], iterate[3]};
+  if (int rc = srbd_pdipm_backward(horizon, batch, sin, grad_x, gr, status, stream)) return rc;
+  return srbd_qp_former_backward(horizon, batch, former_inputs, gr, input_grads, stream);
 }
 
 int srbd_pattern_ccs(int horizon, int which, int* colptr, int* rowind) {

@@ -229,3 +229,117 @@ def mpc_solve(former_inputs: list[torch.Tensor], N: int, n_iter: int, y0: float 
         rc = (L.srbd_mpc_solve_fused if fused else L.srbd_mpc_solve)(*args, _stream_ptr())
     _native.check(rc, "srbd_mpc_solve")
     return buffers.outputs
+
+
+# ---- backward pass: gradients of a loss L(x) through the QP solve and the former ----
+
+def _optional_outputs(outputs, widths, B: int, device, what: str):
+    """None -> every output allocated; a list -> its tensors, None entries stay unwritten (NULL)."""
+    if outputs is None:
+        outputs = [torch.empty((B, w), dtype=torch.float64, device=device) for w in widths]
+    _check_batch(outputs, widths, B, what)
+    return list(outputs)
+
+
+def _ptrs(tensors):
+    return _native.ptr_array([t.data_ptr() if t is not None else 0 for t in tensors])
+
+
+def pdipm_backward(qp: list, iterate: list[torch.Tensor], grad_x: torch.Tensor, N: int,
+                   status: torch.Tensor | None = None, outputs: list | None = None):
+    """The adjoint KKT solve at ``iterate`` = [x, s, z, y] of the QP ``qp`` = [Q_val, G_val, A_val, f, h, b]
+    (f, h, b are not read and may be None) for the seed ``grad_x`` = dL/dx (B, 24N).
+
+    Returns [grad_H, grad_f, grad_A, grad_b, grad_G, grad_d] in qp_former's output order and CCS widths
+    (every nonzero is its own parameter). ``outputs``: preallocated tensors, None entries are skipped.
+    ``status`` (int32 (B,), optional): _native.STATUS_UNSUPPORTED for a QP that is not stage-invariant
+    (its gradients are NaN), STATUS_NONFINITE for a non-finite adjoint. The gradient at a non-converged
+    iterate is the exact derivative of the linearised KKT conditions at that iterate (as in qpth)."""
+    d = Dims(N)
+    B = grad_x.shape[0]
+    ins = list(qp) + list(iterate)
+    _check_batch(ins + [grad_x], d.solver_in_nnz + (d.nz,), B, "pdipm_backward")
+    if any(ins[i] is None for i in (0, 1, 2, 6, 7, 8, 9)):
+        raise ValueError("pdipm_backward: Q_val, G_val, A_val and the iterate x, s, z, y are required")
+    outs = _optional_outputs(outputs, d.former_out_nnz, B, grad_x.device, "pdipm_backward outputs")
+    st = _check_status(status, B, "pdipm_backward")
+    rc = _native.lib().srbd_pdipm_backward(N, B, _ptrs(ins), grad_x.data_ptr(), _ptrs(outs), st, _stream_ptr())
+    _native.check(rc, "srbd_pdipm_backward")
+    return outs
+
+
+def qp_former_backward(former_inputs: list[torch.Tensor], qp_grads: list, N: int, outputs: list | None = None):
+    """The vector-Jacobian product of ``qp_former``: ``qp_grads`` = [grad_H, grad_f, grad_A, grad_b, grad_G,
+    grad_d] (None: a zero gradient) -> the gradients of the 17 former inputs (their order and widths).
+    Those of x and u (inputs 1, 2) are zero: the QP does not depend on the linearisation point.
+    ``outputs``: preallocated tensors, None entries are skipped."""
+    d = Dims(N)
+    B = former_inputs[0].shape[0]
+    _check_batch(former_inputs, d.former_in_nnz, B, "qp_former_backward")
+    _check_batch(qp_grads, d.former_out_nnz, B, "qp_former_backward gradients")
+    outs = _optional_outputs(outputs, d.former_in_nnz, B, former_inputs[0].device, "qp_former_backward outputs")
+    rc = _native.lib().srbd_qp_former_backward(N, B, _ptrs(former_inputs), _ptrs(qp_grads), _ptrs(outs),
+                                               _stream_ptr())
+    _native.check(rc, "srbd_qp_former_backward")
+    return outs
+
+
+def mpc_backward(former_inputs: list[torch.Tensor], iterate: list[torch.Tensor], grad_x: torch.Tensor, N: int,
+                 status: torch.Tensor | None = None, outputs: list | None = None,
+                 workspace: torch.Tensor | None = None):
+    """``srbd_mpc_backward``: qp_former -> pdipm_backward -> qp_former_backward in one call (same bits),
+    from the former inputs, the iterate [x, s, z, y] of the solve and ``grad_x``. Returns the gradients of
+    the 17 former inputs (``outputs``: preallocated tensors, None entries are skipped). ``workspace``:
+    float64, srbd_mpc_backward_workspace_doubles(N, B) elements (allocated when None)."""
+    d = Dims(N)
+    B = former_inputs[0].shape[0]
+    _check_batch(former_inputs, d.former_in_nnz, B, "mpc_backward")
+    _check_batch(list(iterate) + [grad_x], d.solver_in_nnz[6:] + (d.nz,), B, "mpc_backward iterate")
+    outs = _optional_outputs(outputs, d.former_in_nnz, B, grad_x.device, "mpc_backward outputs")
+    L = _native.lib()
+    n = L.srbd_mpc_backward_workspace_doubles(N, B)
+    if workspace is None:
+        workspace = torch.empty(max(n, 1), dtype=torch.float64, device=grad_x.device)
+    if not workspace.is_cuda or workspace.dtype != torch.float64 or workspace.numel() < n or not workspace.is_contiguous():
+        raise ValueError(f"mpc_backward: workspace must be a contiguous CUDA float64 tensor of >= {n} elements")
+    st = _check_status(status, B, "mpc_backward")
+    rc = L.srbd_mpc_backward(N, B, _ptrs(former_inputs), _ptrs(iterate), grad_x.data_ptr(), workspace.data_ptr(),
+                             _ptrs(outs), st, _stream_ptr())
+    _native.check(rc, "srbd_mpc_backward")
+    return outs
+
+
+class _MPCSolveFunction(torch.autograd.Function):
+    """x = mpc_solve(former_inputs): forward ``srbd_mpc_solve_fused``, backward ``srbd_mpc_backward`` on the
+    saved iterate (the adjoint KKT solve and the former's vector-Jacobian product)."""
+
+    @staticmethod
+    def forward(ctx, N, n_iter, y0, *former_inputs):
+        ins = [t.detach().contiguous() for t in former_inputs]
+        x, s, z, y = mpc_solve(ins, N, n_iter, y0)[:4]
+        ctx.N = N
+        ctx.shapes = [t.shape for t in former_inputs]
+        ctx.save_for_backward(*ins, x, s, z, y)
+        return x.clone()  # the saved x stays what the backward pass linearises at
+
+    @staticmethod
+    def backward(ctx, grad_x):
+        saved = ctx.saved_tensors
+        ins, iterate = list(saved[:17]), list(saved[17:])
+        d = Dims(ctx.N)
+        B = ins[0].shape[0]
+        need = ctx.needs_input_grad[3:]
+        outs = [torch.empty((B, w), dtype=torch.float64, device=grad_x.device) if n else None
+                for w, n in zip(d.former_in_nnz, need)]
+        mpc_backward(ins, iterate, grad_x.contiguous(), ctx.N, outputs=outs)
+        return (None, None, None) + tuple(o.view(s) if o is not None else None for o, s in zip(outs, ctx.shapes))
+
+
+def mpc_solve_autograd(former_inputs: list[torch.Tensor], N: int, n_iter: int, y0: float = 1.0) -> torch.Tensor:
+    """The differentiable MPC QP layer: ``x`` (B, 24N) of ``mpc_solve`` (qp_former + cold-started PDIPM,
+    one fused kernel) as a ``torch.autograd.Function``. ``torch.autograd.grad(loss(x), inp)`` works for
+    every former input that requires grad (x and u, the linearisation point, get zeros; inputs without
+    ``requires_grad`` get None). The gradient is that of the linearised KKT conditions at the returned
+    iterate: exact at convergence, and within 0.1-1 % of finite differences of the solve at 35
+    iterations (DESIGN.md)."""
+    return _MPCSolveFunction.apply(N, n_iter, float(y0), *former_inputs)

@@ -321,6 +321,48 @@ int srbd_u0_wrench_torque(int horizon, int batch, const double* x, const float* 
 int srbd_dense_scatter(int batch, int nnz, int rc, const int* inverse_index, const double* values,
                        double* dense, void* stream);
 
+/* ---- Backward pass: gradients of a loss L(x) through the QP solve and the former --------------------
+ * The iterate (x, s, z, y) a solve returned is read as a root of the solver's regularised KKT
+ * conditions; their Newton matrix K is symmetric, so one solve of
+ *   K [lx; ls; lz; ly] = [grad_x; 0; 0; 0]
+ * (one factorisation, one solve, one refinement step, the forward LDS-resident kernel's phases) gives
+ * every gradient. At a non-converged iterate this is the exact derivative of the linearised KKT
+ * conditions at that iterate (qpth's convention). Only a seed on x is taken: seeds on s, z and y are
+ * out of scope. All entry points: host arrays of device pointers, asynchronous on `stream`, no device
+ * allocation (capture-safe after srbd_prepare_device), batch == 0 and bad arguments return without
+ * touching the GPU, errors through srbd_last_error().
+ *
+ * Status bit of the backward entry points: the QP is not stage-invariant (any CCS input other than
+ * qp_former's output). Such a QP is not differentiated: its gradients are NaN. SRBD_STATUS_NONFINITE
+ * reports a NaN / Inf in the adjoint of a QP that was solved. */
+#define SRBD_STATUS_UNSUPPORTED 8
+
+/* inputs: srbd_pdipm's ten, in its order (Q_val, G_val, A_val, f, h, b, x, s, z, y); f, h, b are not
+ * read and may be NULL. grad_x (B, 24N) = dL/dx. qp_grads: six outputs in qp_former's output order and
+ * CCS widths, each skipped when NULL (asking for a subset changes no bit of the others):
+ *   grad_H (24N)       -lx[c] x[c]                      grad_f (24N)  -lx
+ *   grad_A (122N-24)   -(lx[c] y[r] + ly[r] x[c])       grad_b (14N)   ly
+ *   grad_G (28N)       -(lx[c] z[r] + lz[r] x[c])       grad_d (16N)   lz
+ * Every CCS nonzero is its own parameter (nothing is summed over stages). status (B ints) may be NULL.
+ * An env's gradients have the same bits at any batch size and position. Horizons 1..32. */
+int srbd_pdipm_backward(int horizon, int batch, const double* const* inputs, const double* grad_x,
+                        double* const* qp_grads, int* status, void* stream);
+
+/* The vector-Jacobian product of srbd_qp_former: qp_grads (six, qp_former's output order; NULL = a zero
+ * gradient) -> input_grads (17, the former inputs' order and widths; NULL = not written). The gradients
+ * of x and u (inputs 1 and 2) are zero: the model is affine, so the QP does not depend on the
+ * linearisation point. R_body and I_world are decoded column-major, as the former reads them. */
+int srbd_qp_former_backward(int horizon, int batch, const double* const* former_inputs,
+                            const double* const* qp_grads, double* const* input_grads, void* stream);
+
+/* srbd_qp_former -> srbd_pdipm_backward -> srbd_qp_former_backward in one call (same bits): the QP and
+ * its six gradients go to `workspace`, caller-owned device memory of
+ * srbd_mpc_backward_workspace_doubles(horizon, batch) doubles. iterate: x, s, z, y of the solve. */
+size_t srbd_mpc_backward_workspace_doubles(int horizon, int batch);
+int srbd_mpc_backward(int horizon, int batch, const double* const* former_inputs,
+                      const double* const* iterate /* x, s, z, y */, const double* grad_x,
+                      double* workspace, double* const* input_grads, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
