@@ -29,7 +29,13 @@ NAMES = ["grad_H", "grad_f", "grad_A", "grad_b", "grad_G", "grad_d"]
 
 @functools.lru_cache(maxsize=None)
 def workload(N: int, gait: str):
-    """(former inputs, QP in the solver's input order [H, G, A, f, d, b]) as numpy arrays."""
+    """(former inputs, QP in the solver's input order [H, G, A, f, d, b]) as numpy arrays. `gait` names the
+    workload: "fixed" / "random" (make_workload), or "generic" (tests/_generic.py adjoint_workload: per-env
+    scalars, asymmetric inertia, a generic linearisation point); iterate, reference and reduced_floor below
+    take the same name."""
+    if gait == "generic":
+        from tests import _generic
+        return _generic.adjoint_workload(N)
     wl = make_workload(BATCH, N, seed=900 + N, random_gait=(gait == "random"))
     H, f, A, b, G, d = oracle.qp_former(N, wl.inputs)
     return wl.inputs, [H, G, A, f, d, b]

@@ -68,11 +68,9 @@ class _Root:
         return br.split(N, w)[0]
 
 
-@pytest.fixture(scope="module")
-def adjoint_case():
+def _adjoint_case(former_inputs):
     N, K = 2, 5
-    wl = make_workload(2, N, seed=41, random_gait=True, residuals=True)
-    H, f, A, b, G, d = [a[1] for a in oracle.qp_former(N, wl.inputs)]
+    H, f, A, b, G, d = [a[1] for a in oracle.qp_former(N, former_inputs)]
     it = solver_init(d[None], N)
     out = oracle.pdipm(N, K, [H, G, A, f, d, b] + [v[0] for v in it])
     w0 = [np.asarray(out[k]).reshape(-1) for k in range(4)]
@@ -83,9 +81,31 @@ def adjoint_case():
     return N, theta, w0, g, grads
 
 
+@pytest.fixture(scope="module")
+def adjoint_case():
+    return _adjoint_case(make_workload(2, 2, seed=41, random_gait=True, residuals=True).inputs)
+
+
+@pytest.fixture(scope="module")
+def adjoint_case_generic():
+    """The same N = 2, K = 5 case with the QP of a generic env (tests/_generic.py: its own dt, mass, mu, Q, R,
+    asymmetric inertia, a generic linearisation point)."""
+    from tests._generic import generic_former_inputs
+    return _adjoint_case(generic_former_inputs(2, 2, seed=41, solvable=True))
+
+
 @pytest.mark.parametrize("which", ["H", "f", "A", "b", "G", "d", "all"])
 def test_adjoint_gradients_match_central_differences_of_the_frozen_root(adjoint_case, which):
-    N, theta, w0, g, grads = adjoint_case
+    _check_adjoint_against_central_differences(adjoint_case, which)
+
+
+@pytest.mark.parametrize("which", ["H", "f", "A", "b", "G", "d", "all"])
+def test_adjoint_gradients_match_central_differences_at_a_generic_point(adjoint_case_generic, which):
+    _check_adjoint_against_central_differences(adjoint_case_generic, which)
+
+
+def _check_adjoint_against_central_differences(case, which):
+    N, theta, w0, g, grads = case
     root = _Root(N, theta, w0)
     assert np.abs(root.solve(theta) - w0[0]).max() <= 1e-12 * np.abs(w0[0]).max()  # w0 is the root
     rng = np.random.default_rng(100 + sum(map(ord, which)))

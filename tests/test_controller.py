@@ -163,6 +163,62 @@ def test_prepare_inputs_matches_oracle(gait, literal):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("literal", [True, False])
+@pytest.mark.parametrize("N", [1, 10, 32])
+def test_prepare_inputs_matches_oracle_at_the_branch_edges(N, literal):
+    """The same bit-for-bit comparison at N = 1 and 32 (the 12N loop makes six passes) as well, with envs
+    forced onto the edges of the kernel's branches:
+      * v_x at float32(1e-2), the stationary threshold, and its two float32 neighbours, both signs, with and
+        without first_run;
+      * gait_phase at 0, at float32(k / cycle) for k = 1, cycle / 2, cycle - 1 and the float32 just below each
+        (phase * cycle then truncates to k or k - 1), and at 0.99999994 = 1 - 2^-24, the largest phase below 1:
+        the float32 product cycle - cycle 2^-24 lies more than half an ulp below cycle for every cycle that is
+        no power of two and is exact for one that is, so it never rounds up to cycle and truncates to
+        cycle - 1 (asserted);
+      * a zero-length cycle (ssp = dsp = 0), where the reference would fault on % 0: the documented result,
+        both feet in contact at every stage, asserted directly."""
+    B = 96
+    st, cmd, ctrl, params, gait_args, table = random_robot(B, 71 + N, N, gait=True)
+    f32 = np.float32
+    thr = f32(1e-2)
+    vx = [thr, np.nextafter(thr, f32(1.0)), np.nextafter(thr, f32(0.0))]
+    vx = np.array(vx + [-v for v in vx], f32)
+    for off in (0, 7, 14):  # first_run = (env % 3 == 0): every value meets it set in one group, clear in two
+        cmd["desired_velocity_b"][off:off + 6, 0] = vx
+    assert np.array_equal(np.abs(cmd["desired_velocity_b"][0:3, 0]) < thr, [False, False, True])
+    phase, ssp, dsp = (np.array(a) for a in gait_args)
+    cyc = (ssp + dsp).sum(axis=1)
+    e = 20
+    phase[e] = 0.0
+    for env_cyc_k in (1, None, -1):
+        for below in (False, True):
+            e += 1
+            k = cyc[e] // 2 if env_cyc_k is None else env_cyc_k % cyc[e]
+            p = f32(k) / f32(cyc[e])
+            phase[e] = np.nextafter(p, f32(0.0)) if below else p
+    last = slice(e + 1, e + 9)  # eight envs, cycles 6 .. 16
+    phase[last] = f32(0.99999994)
+    assert phase[e + 1] == np.nextafter(f32(1.0), f32(0.0))
+    assert np.array_equal((phase[last] * cyc[last].astype(f32)).astype(np.int64), cyc[last] - 1)
+    zero = slice(40, 44)
+    ssp[zero] = 0
+    dsp[zero] = 0
+    gait_args = (phase, ssp, dsp)
+    c = _controller(B, N, st, cmd, ctrl, params, gait_args, table, literal)
+    got = [t.cpu().numpy() for t in c.prepare()]
+    torch.cuda.synchronize()
+    with np.errstate(divide="ignore"):  # the restatement's % 0 gives step 0: no phase matches, double support
+        ref, new = mpc_io.prepare_inputs(N, st, cmd, ctrl, params, gait=gait_args, contact_table=table,
+                                         literal=literal)
+    for k, (g, r) in enumerate(zip(got, ref)):
+        assert np.array_equal(g, r), f"former input {k}: max diff {np.abs(g - r).max():.3e}"
+    assert np.array_equal(c.world_position_desired.cpu().numpy(), new["world_position_desired"])
+    assert np.array_equal(c.yaw_desired.cpu().numpy(), new["yaw_desired"])
+    assert not c.first_run.any()
+    assert np.all(got[12][zero] == 1.0)
+
+
+@pytest.mark.gpu
 def test_u0_wrench_matches_oracle():
     from biped_pympc_amd import _native, solver
     N, B = 10, 1000
