@@ -10,10 +10,13 @@ takes ~3 h for 5 unrolled Newton iterations (README.md:80-84); this builds in se
 """
 from __future__ import annotations
 
+import contextlib
 import hashlib
 import os
 import re
 import subprocess
+import sys
+import tempfile
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
@@ -63,10 +66,12 @@ def _digest(parts) -> str:
     return h.hexdigest()[:16]
 
 
-def core_sources() -> list[str]:
-    """Every file libsrbd_mpc.so is compiled from: the HIP units, their headers, the C-ABI header."""
-    srcs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".hpp"))]
-    return srcs + [os.path.join(INCLUDE, "srbd_mpc.h")]
+def core_sources(csrc: str | None = None) -> list[str]:
+    """Every file libsrbd_mpc.so is compiled from: the HIP units, their headers, the C-ABI header
+    (which srbd_mpc.hip includes as ../../include/srbd_mpc.h, so it is found relative to `csrc`)."""
+    csrc = os.path.abspath(csrc or CSRC)
+    srcs = [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".hpp"))]
+    return srcs + [os.path.join(os.path.dirname(os.path.dirname(csrc)), "include", "srbd_mpc.h")]
 
 
 def source_hash(sources: list[str] | None = None) -> str:
@@ -79,14 +84,13 @@ def source_hash(sources: list[str] | None = None) -> str:
     return _digest(parts)
 
 
-def _unit_hash(unit: str, bid: str) -> str:
-    """What one object file depends on: its unit, every header (csrc/*.hpp, include/srbd_mpc.h), the
-    flags, and -- for the main unit, which embeds it -- the library's build id."""
-    parts = [ARCH, unit, repr(HIP_UNITS[unit]), repr(_COMMON_FLAGS), bid if unit == "srbd_mpc.hip" else ""]
-    for s in core_sources():
-        if s.endswith(".hip") and os.path.basename(s) != unit:
-            continue
-        if s.endswith(".h") and unit != "srbd_mpc.hip":  # only the main unit includes the C-ABI header
+def _unit_hash(unit: str, cmd: list[str], sources: list[str]) -> str:
+    """What one object file depends on: its flags (for the main unit they carry the library's build
+    id, which it embeds), its source and every header (csrc/*.hpp; include/srbd_mpc.h for the main
+    unit, the only one that includes it)."""
+    parts = [unit, repr(cmd[1:cmd.index("-o")])]
+    for s in [cmd[-1]] + [h for h in sources if not h.endswith(".hip")]:
+        if s.endswith(".h") and unit != "srbd_mpc.hip":
             continue
         parts += [os.path.basename(s), open(s, "rb").read()]
     return _digest(parts)
@@ -138,16 +142,18 @@ HIP_UNITS = {
 _COMMON_FLAGS = ["-O3", "-std=c++17"]
 
 
-def unit_compile_cmd(unit: str, extra: list[str]) -> list[str]:
-    """hipcc command line of one translation unit exactly as the product build compiles it (the
-    ISA audit, tests/test_isa_hazards.py, appends --cuda-device-only -S to the same flags)."""
-    return [HIPCC, f"--offload-arch={ARCH}", *_COMMON_FLAGS, *HIP_UNITS[unit], *extra,
-            os.path.join(CSRC, unit)]
+def unit_compile_cmd(unit: str, extra: list[str], csrc: str | None = None, replace: dict | None = None) -> list[str]:
+    """hipcc command line of one translation unit exactly as the product build compiles it: the one
+    constructor of a unit's command line, for the product, the variants (build_core) and the ISA
+    listings (isa_listings). `csrc` is another source directory, `replace` maps a unit to the file
+    compiled in its place."""
+    src = (replace or {}).get(unit) or os.path.join(csrc or CSRC, unit)
+    return [HIPCC, f"--offload-arch={ARCH}", *_COMMON_FLAGS, *HIP_UNITS[unit], *extra, src]
 
 
 def _compile_parallel(cmds: list[list[str]]) -> None:
-    """Run independent compiles at once; on any failure the others are killed and reaped before
-    raising, so no orphan keeps writing objects into lib/."""
+    """Run independent compiles at once and pass their diagnostics on; on any failure the others are
+    killed and reaped before raising, so no orphan keeps writing objects into lib/."""
     procs = [subprocess.Popen(c, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for c in cmds]
     failed = None
     try:
@@ -156,6 +162,7 @@ def _compile_parallel(cmds: list[list[str]]) -> None:
             if pr.returncode != 0:
                 failed = f"build failed: {' '.join(c)}\n{out}\n{err}"
                 break
+            sys.stderr.write(err)
     finally:
         for pr in procs:
             if pr.poll() is None:
@@ -165,46 +172,80 @@ def _compile_parallel(cmds: list[list[str]]) -> None:
         raise RuntimeError(failed)
 
 
+def build_core(out: str, csrc: str | None = None, flags=(), unit_flags: dict | None = None,
+               replace: dict | None = None, objdir: str | None = None, force: bool = True,
+               verbose: bool = False) -> dict[str, list[str]]:
+    """Compile the units of HIP_UNITS with their flags and link them into `out`: the one recipe of
+    libsrbd_mpc.so, for the product (build()) and for every variant (scripts/build_variant.py).
+      csrc        source directory (default: the package's). A patched copy keeps the
+                  biped_pympc_amd/csrc + include layout, as srbd_mpc.hip includes ../../include/srbd_mpc.h
+      flags       extra flags for every unit, after the product's
+      unit_flags  {unit: extra flags}, e.g. a force-included header that may go into one unit only
+      replace     {unit: source file compiled in its place}
+      objdir      where the objects go (default: a temporary directory). Unless `force`, an object there
+                  is reused when its .id sidecar records the hash of exactly what it was compiled from
+    The embedded build id is source_hash() of `csrc`, digested again with the extra flags and the
+    replacements where there are any: only identical sources and flags give the product's id.
+    Returns {unit: command line} of the units it compiled."""
+    sources = core_sources(csrc)
+    unit_flags, replace = unit_flags or {}, {u: os.path.abspath(f) for u, f in (replace or {}).items()}
+    bid = source_hash(sources)
+    if flags or unit_flags or replace:
+        bid = _digest([bid, repr(list(flags)), repr(sorted(unit_flags.items())),
+                       *[x for u, f in sorted(replace.items()) for x in (u, open(f, "rb").read())]])
+    with tempfile.TemporaryDirectory() if objdir is None else contextlib.nullcontext(objdir) as od:
+        # srbd_build_id() is defined in the main unit; the id names the sources and flags of all units
+        objs = {u: os.path.join(od, u.replace(".hip", ".o")) for u in HIP_UNITS}
+        cmds = {u: unit_compile_cmd(u, [*flags, *unit_flags.get(u, []), "-fPIC", "-c",
+                                        *([f'-DSRBD_BUILD_ID="{bid}"'] if u == "srbd_mpc.hip" else []),
+                                        "-o", o], csrc, replace) for u, o in objs.items()}
+        ids = {u: _unit_hash(u, c, sources) for u, c in cmds.items()}
+        stale = {u: c for u, c in cmds.items() if force or not (
+            os.path.exists(objs[u]) and os.path.exists(objs[u] + ".id") and open(objs[u] + ".id").read().strip() == ids[u])}
+        tmp = out + ".tmp"
+        link = [HIPCC, f"--offload-arch={ARCH}", "-fPIC", "-shared", "-o", tmp, *objs.values()]
+        for c in [*stale.values(), link] if verbose else []:
+            print(" ".join(c))
+        for u in stale:  # no sidecar describes an object while it is rewritten
+            if os.path.exists(objs[u] + ".id"):
+                os.remove(objs[u] + ".id")
+        _compile_parallel(list(stale.values()))  # independent translation units
+        for u in stale:
+            with open(objs[u] + ".id", "w") as fh:
+                fh.write(ids[u] + "\n")
+        _run(link)
+    os.replace(tmp, out)  # a process that has the old library mapped keeps its copy
+    if embedded_id(out) != bid:
+        raise RuntimeError(f"{out}: build id {embedded_id(out)} != {bid}")
+    return stale
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(LIB_DIR, exist_ok=True)
     core = os.path.join(LIB_DIR, "libsrbd_mpc.so")
     bid = source_hash()
     if force or embedded_id(core) != bid:
-        objs = [os.path.join(LIB_DIR, u.replace(".hip", ".o")) for u in HIP_UNITS]
-        # srbd_build_id() is defined in the main unit; the id names the sources and flags of all units.
-        # An object is reused when its sidecar records the hash of exactly what it was compiled from.
-        stale = []
-        for u, o in zip(HIP_UNITS, objs):
-            uh = _unit_hash(u, bid)
-            try:
-                same = not force and open(o + ".id").read().strip() == uh and os.path.exists(o)
-            except OSError:
-                same = False
-            if not same:
-                stale.append((u, o, uh))
-        units = [unit_compile_cmd(u, ["-fPIC", "-c", *([f'-DSRBD_BUILD_ID="{bid}"'] if u == "srbd_mpc.hip" else []),
-                                      "-o", o]) for u, o, _ in stale]
-        for cmd in units:
-            if verbose:
-                print(" ".join(cmd))
-        for _, o, _ in stale:
-            if os.path.exists(o + ".id"):
-                os.remove(o + ".id")
-        _compile_parallel(units)  # independent translation units
-        for _, o, uh in stale:
-            with open(o + ".id", "w") as fh:
-                fh.write(uh + "\n")
-        tmp = core + ".tmp"
-        link = [HIPCC, f"--offload-arch={ARCH}", "-fPIC", "-shared", "-o", tmp, *objs]
-        if verbose:
-            print(" ".join(link))
-        _run(link)
-        os.replace(tmp, core)  # a process that has the old library mapped keeps its copy
+        build_core(core, objdir=LIB_DIR, force=force, verbose=verbose)
         if embedded_id(core) != bid:
             raise RuntimeError(f"{core}: build id {embedded_id(core)} != source hash {bid}")
     for fn, N, K in DROPIN_CONFIGS:
         _build_dropin_lib(fn, N, K, core, force, verbose)
     return core
+
+
+REGN_PARTS = 6  # csrc/srbd_regN.hip SRBD_REGN_PART: its horizons in six parts, for ISA listings
+
+
+def isa_listings(outdir: str, units=None) -> dict[str, list[str]]:
+    """Device ISA of the given units (default: all) as the product compiles them: {unit: .s files},
+    srbd_regN.hip in its REGN_PARTS horizon parts, everything compiled concurrently."""
+    outs, cmds = {}, []
+    for u in HIP_UNITS if units is None else units:
+        parts = [[f"-DSRBD_REGN_PART={k}"] for k in range(REGN_PARTS)] if u == "srbd_regN.hip" else [[]]
+        outs[u] = [os.path.join(outdir, f"{u}.{k}.s") for k in range(len(parts))]
+        cmds += [unit_compile_cmd(u, [*defs, "--cuda-device-only", "-S", "-o", o]) for defs, o in zip(parts, outs[u])]
+    _compile_parallel(cmds)
+    return outs
 
 
 # ---- test-only primitive harness (tests/csrc/prim_harness.hip -> tests/libprim_harness.so) ----

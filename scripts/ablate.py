@@ -6,16 +6,9 @@ product sources are never modified; see scripts/build_variant.py for the build f
 Each variant runs one idempotent phase twice per Newton iteration, so (variant - base) is that
 phase's marginal cost in the real 2-waves/SIMD context. Timing: scripts/ab_bench.sh-style runs of
 bench.py with SRBD_LIB=OUT on the GPU box."""
-import os
-import shutil
-import subprocess
 import sys
-import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "biped_pympc_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
-REG = "pdipm_srbd_reg.hpp"
+from build_variant import build_variant, patched_csrc
 
 
 def _dup(src: str, start: str, end: str) -> str:
@@ -149,25 +142,8 @@ VARIANTS = {
 
 
 def build(out: str, name: str) -> str:
-    with tempfile.TemporaryDirectory() as td:
-        d = os.path.join(td, "biped_pympc_amd", "csrc")
-        shutil.copytree(CSRC, d)
-        shutil.copytree(os.path.join(ROOT, "include"), os.path.join(td, "include"))
-        p = os.path.join(d, REG)
-        src = open(p).read()
-        new = VARIANTS[name](src)
-        assert new != src, name
-        open(p, "w").write(new)
-        o20, om = os.path.join(td, "reg20.o"), os.path.join(td, "main.o")
-        base = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", "-I", os.path.join(ROOT, "include")]
-        on = os.path.join(td, "regN.o")
-        trk = ["-mllvm", "-amdgpu-use-amdgpu-trackers=1"]
-        procs = [subprocess.Popen(base + trk + ["-o", o20, os.path.join(d, "srbd_reg20.hip")]),
-                 subprocess.Popen(base + trk + ["-o", on, os.path.join(d, "srbd_regN.hip")]),
-                 subprocess.Popen(base + ["-DSRBD_SPLIT_REG20", "-o", om, os.path.join(d, "srbd_mpc.hip")])]
-        if any(p.wait() for p in procs):
-            raise SystemExit(f"variant {name}: compile failed")
-        subprocess.run([HIPCC, "--offload-arch=gfx950", "-fPIC", "-shared", "-o", out, om, o20, on], check=True)
+    with patched_csrc(VARIANTS[name]) as d:  # pdipm_srbd_reg.hpp, every unit rebuilt from the copy
+        build_variant(out, csrc=d)
     return out
 
 

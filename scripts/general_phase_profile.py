@@ -4,15 +4,15 @@
                                                            GPROF_LIB=<name> picks the file name)
   python scripts/general_phase_profile.py run [N] [B] [K] (GPU box: general path, prints cycles per QP)
 
-The instrumented library is srbd_mpc.hip compiled with scripts/phase_prof.hpp force-included (the
-PROF_* markers become stamps; the product build's are empty), linked with the product's objects of
-the other two units. Phases: 0 residuals, 1 factor (W, Phi_u, S_ii), 2 factor chain, 3 solve
+The instrumented library is a scripts/build_variant.py variant with scripts/phase_prof.hpp
+force-included in srbd_mpc.hip, the unit of the general solve (the PROF_* markers become stamps; the
+product build's are empty), and without the srbd_regN.hip unit, which the general path never enters.
+Phases: 0 residuals, 1 factor (W, Phi_u, S_ii), 2 factor chain, 3 solve
 right-hand side and Phi^-1, 4 forward chain, 5 backward chain, 6 dx / dz / ds finish, 7 refinement
 residuals, 8 step lengths / sigma / update. Cycles of one QP (lane 0 of its wave), per iteration.
 """
 import ctypes
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,12 +23,9 @@ NAMES = ["residuals", "factor: W, Phi_u, S_ii", "factor: chain", "solve: rhs, Ph
 
 
 def build():
-    from biped_pympc_amd.build import HIPCC, LIB_DIR, unit_compile_cmd
-    obj = "/tmp/srbd_mpc_gprof.o"
-    subprocess.run(unit_compile_cmd("srbd_mpc.hip", ["-include", os.path.join(ROOT, "scripts", "phase_prof.hpp"),
-                                                      "-fPIC", "-c", "-o", obj]), check=True)
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-fPIC", "-shared", "-o", LIB, obj,
-                    os.path.join(LIB_DIR, "srbd_reg20.o"), os.path.join(LIB_DIR, "srbd_regN.o")], check=True)
+    from build_variant import PHASE_PROF, build_variant
+    os.makedirs(os.path.dirname(LIB), exist_ok=True)
+    build_variant(LIB, regn=False, unit_flags={"srbd_mpc.hip": PHASE_PROF})
     print(LIB)
 
 

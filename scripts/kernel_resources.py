@@ -2,8 +2,8 @@
 
     python scripts/kernel_resources.py /tmp/main.s [substring]
     python scripts/kernel_resources.py --table > profiles/rNN/kernel_resources.txt
-        (compiles every product unit to device ISA with the product flags, srbd_regN.hip in its six
-        horizon parts, and prints one row per kernel)
+        (lists every product unit's device ISA with biped_pympc_amd/build.py isa_listings and prints
+        one row per kernel)
 """
 import re
 import sys
@@ -71,25 +71,16 @@ def table(tmpdir="/tmp/kernel_resources"):
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sys.path.insert(0, root)
-    from biped_pympc_amd.build import HIP_UNITS, source_hash, unit_compile_cmd
+    from biped_pympc_amd.build import isa_listings, source_hash
     os.makedirs(tmpdir, exist_ok=True)
-    jobs = []
-    for unit in HIP_UNITS:
-        parts = [[f"-DSRBD_REGN_PART={k}"] for k in range(6)] if unit == "srbd_regN.hip" else [[]]
-        for k, defs in enumerate(parts):
-            out = os.path.join(tmpdir, f"{unit}.{k}.s")
-            tag = f"{unit}/{k}" if len(parts) > 1 else unit
-            cmd = unit_compile_cmd(unit, [*defs, "--cuda-device-only", "-S", "-o", out])
-            jobs.append((tag, out, subprocess.Popen(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE)))
     rows = []
-    for tag, out, p in jobs:
-        err = p.communicate()[1]
-        if p.returncode:
-            raise SystemExit(err.decode()[-2000:])
-        for name, r in resources(out).items():
-            dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
-            dem = re.sub(r"\(.*\)$", "", dem)
-            rows.append((tag, dem, r))
+    for unit, outs in isa_listings(tmpdir).items():
+        for k, out in enumerate(outs):
+            tag = f"{unit}/{k}" if len(outs) > 1 else unit
+            for name, r in resources(out).items():
+                dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
+                dem = re.sub(r"\(.*\)$", "", dem)
+                rows.append((tag, dem, r))
     print(f"# Per-kernel resources from the gfx950 device ISA (hipcc --cuda-device-only -S, product flags;\n"
           f"# scripts/kernel_resources.py --table). Sources at build id {source_hash()}. vgpr = arch VGPRs, spill =\n"
           f"# VGPR spills as the compiler reports them (the CCS kernels' one or two: the whole-wave save around the\n"

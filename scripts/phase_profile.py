@@ -6,18 +6,16 @@ Run on the GPU box: python scripts/phase_profile.py [N] [B] [K]
 """
 import ctypes
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from build_variant import PHASE_PROF, build_variant, needs_regn, reg_unit
+
+N = int(sys.argv[1]) if len(sys.argv) > 1 else 10
 LIB = os.environ.get("PHASE_LIB")  # prebuilt instrumented library (N = 20: scripts/build_variant.py
 #   OUT --no-regn --reg20=-include --reg20=scripts/phase_prof.hpp, stamps in the N = 20 unit only)
-if not LIB:
+if not LIB:  # the stamps go into the one unit that holds the horizon's register kernels
     LIB = "/tmp/libsrbd_mpc_prof.so"
-    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-                    "-include", os.path.join(ROOT, "scripts", "phase_prof.hpp"), "-o", LIB,
-                    os.path.join(ROOT, "biped_pympc_amd/csrc/srbd_mpc.hip")], check=True)
+    build_variant(LIB, regn=needs_regn(N), unit_flags={reg_unit(N): PHASE_PROF})
 os.environ["SRBD_LIB"] = LIB
 
 import numpy as np  # noqa: E402
@@ -26,7 +24,6 @@ import torch  # noqa: E402
 from biped_pympc_amd import _native, solver  # noqa: E402
 from biped_pympc_amd.utils.synthetic import make_workload  # noqa: E402
 
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 10
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 4096
 K = int(sys.argv[3]) if len(sys.argv) > 3 else 10
 L = _native.lib()

@@ -8,13 +8,10 @@ and f/b/d set-up, per-QP constants (C, K0, K1, slot tables), iterate init; and t
 """
 import ctypes
 import os
-import shutil
-import subprocess
 import sys
-import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from build_variant import PHASE_PROF, ROOT, build_variant, needs_regn, patched_csrc, reg_unit
+
 LIB = os.path.join(ROOT, "ab", "libsrbd_mpc_prologue.so")  # built on the CPU host (ab/ is not in git)
 
 
@@ -30,34 +27,29 @@ def patch(src: str) -> str:
     rep("  PROF_MARK_CTX(C);\n  const int n_iter", "  PROF_ADD_CTX(C, 11);\n  const int n_iter")
     rep("  PROF_FLUSH(C);\n  auto outp", "  PROF_ADD_CTX(C, 7);\n  auto outp")
     # epilogue stamp + the single flush at the very end of the body
-    i = src.index("// 2 waves per SIMD: 2 one-wave QPs")
+    i = src.index("// Device code generation of the register kernels")  # what follows reg_kernel_body
     j = src.rindex("}\n", 0, i)
     src = src[:j] + "  PROF_ADD_CTX(C, 12);\n  PROF_FLUSH(C);\n" + src[j:]
     return src
 
 
-def build():
-    with tempfile.TemporaryDirectory() as td:
-        d = os.path.join(td, "biped_pympc_amd", "csrc")  # srbd_mpc.hip includes ../../include/srbd_mpc.h
-        shutil.copytree(os.path.join(ROOT, "biped_pympc_amd", "csrc"), d)
-        shutil.copytree(os.path.join(ROOT, "include"), os.path.join(td, "include"))
-        p = os.path.join(d, "pdipm_srbd_reg.hpp")
-        src = patch(open(p).read())
-        open(p, "w").write(src)
-        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-                        "-include", os.path.join(ROOT, "scripts", "phase_prof.hpp"), "-I", os.path.join(ROOT, "include"), "-o", LIB,
-                        os.path.join(d, "srbd_mpc.hip")], check=True)
+def build(N):
+    """The stamps go into the one unit that holds the horizon's register kernels; the library serves
+    that horizon (the others run unstamped, or on the LDS-resident kernels without srbd_regN.hip)."""
+    os.makedirs(os.path.dirname(LIB), exist_ok=True)
+    with patched_csrc(patch) as d:
+        build_variant(LIB, regn=needs_regn(N), unit_flags={reg_unit(N): PHASE_PROF}, csrc=d)
 
 
 def main():
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    N = int(args[0]) if args else 10
     if not os.path.exists(LIB) or "--rebuild" in sys.argv:
-        build()
+        build(N)
     os.environ["SRBD_LIB"] = LIB
     import torch
     from biped_pympc_amd import _native, solver
     from biped_pympc_amd.utils.synthetic import make_workload
-    args = [a for a in sys.argv[1:] if not a.startswith("--")]
-    N = int(args[0]) if args else 10
     B = int(args[1]) if len(args) > 1 else 4096
     K = int(args[2]) if len(args) > 2 else 10
     L = _native.lib()

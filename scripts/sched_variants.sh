@@ -1,5 +1,7 @@
 # Compile the kernel library under LLVM scheduler variants (CPU, cross-compiled) and print the fused
-# kernels' register use / spills per variant; the libraries land in /tmp/vs/<name>.so.
+# kernels' register use / spills per variant; the libraries land in /tmp/vs/<name>.so. Each is a
+# scripts/build_variant.py variant: the flags go on top of the product's per-unit flags (so "trk"
+# changes the main unit only, the N = 20 unit has the trackers already), without the srbd_regN.hip unit.
 # Timing on the GPU box: scripts/variant_bench.py NAME="FLAGS" ... (builds its own copies there).
 set -e
 mkdir -p /tmp/vs
@@ -15,8 +17,7 @@ VARIANTS=(
 )
 for v in "${VARIANTS[@]}"; do
   n=${v%%:*}; f=${v#*:}
-  ( /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared $f -I "$ROOT/include" \
-      -Rpass-analysis=kernel-resource-usage -o /tmp/vs/$n.so "$ROOT/biped_pympc_amd/csrc/srbd_mpc.hip" \
+  ( python "$ROOT/scripts/build_variant.py" /tmp/vs/$n.so --no-regn $f -Rpass-analysis=kernel-resource-usage \
       > /tmp/vs/$n.log 2>&1; echo "$n rc=$?" ) &
 done
 wait

@@ -1,8 +1,8 @@
 """Fused-step A/B of compile-time variants on one GPU box (the bench's own kernel and timing).
 
 python scripts/variant_bench.py [--horizon N] [--rounds R] [--batch B] NAME=FLAGS [NAME=FLAGS ...]
-Each variant is built from the working tree's csrc with its -D flags into /tmp/libsrbd_mpc_<NAME>.so;
-the variants then run bench.py (--steps 50, SRBD_LIB) in turn, R rounds, and the fused kernel's
+Each variant is the product build plus its flags (scripts/build_variant.py; without the srbd_regN.hip
+unit when the horizon is 10 or 20) in /tmp/libsrbd_mpc_<NAME>.so; the variants then run bench.py (--steps 50, SRBD_LIB) in turn, R rounds, and the fused kernel's
 HIP-event time per launch is printed per run and as the per-variant median.
 """
 import argparse
@@ -12,7 +12,7 @@ import statistics
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from build_variant import ROOT, build_variant, needs_regn
 
 
 def main():
@@ -25,11 +25,8 @@ def main():
     libs = {}
     for spec in a.variants:
         name, _, flags = spec.partition("=")
-        lib = f"/tmp/libsrbd_mpc_{name}.so"
-        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-                        *flags.split(), "-I", os.path.join(ROOT, "include"), "-o", lib,
-                        os.path.join(ROOT, "biped_pympc_amd/csrc/srbd_mpc.hip")], check=True)
-        libs[name] = lib
+        libs[name] = f"/tmp/libsrbd_mpc_{name}.so"
+        build_variant(libs[name], flags.split(), regn=needs_regn(a.horizon))
     res = {n: [] for n in libs}
     for _ in range(a.rounds):
         for name, lib in libs.items():

@@ -3,7 +3,9 @@
 python scripts/variant_counters.py NAME=FLAGS[@CSRC_DIR] [...]
   e.g. base= rep_build=-DSRBD_REPEAT_PHASE=4 old=@/path/to/other/csrc
 
-Each variant: hipcc -> /tmp/libsrbd_mpc_<NAME>.so; ms per launch from scripts/kernel_ab.py
+Each variant: scripts/build_variant.py (the product build plus FLAGS, from CSRC_DIR where given: the
+current unit list applied to a directory that lies two levels below its include/, as ab/head_csrc
+does) -> /tmp/libsrbd_mpc_<NAME>.so; ms per launch from scripts/kernel_ab.py
 (N=10, B=4096, K=10, auto path = register kernel), then one rocprofv3 --pmc pass of the same command
 (SQ_INSTS_VALU, SQ_INSTS_LDS, SQ_LDS_BANK_CONFLICT, SQ_WAVE_CYCLES) summarised per wave.
 """
@@ -13,7 +15,8 @@ import os
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from build_variant import ROOT, build_variant, needs_regn
+
 HORIZON = os.environ.get("VC_N", "10")  # horizon of the measured solver kernel
 KERNEL = f"pdipm_srbd_reg_kernel<{HORIZON}>"
 COUNTERS = ["SQ_INSTS_VALU", "SQ_INSTS_LDS", "SQ_LDS_BANK_CONFLICT", "SQ_WAVE_CYCLES"]
@@ -24,11 +27,8 @@ def main():
     for spec in sys.argv[1:]:
         name, _, flags = spec.partition("=")
         flags, _, csrc = flags.partition("@")
-        csrc = csrc or os.path.join(ROOT, "biped_pympc_amd/csrc")
         lib = f"/tmp/libsrbd_mpc_{name}.so"
-        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-                        *flags.split(), "-I", os.path.join(ROOT, "include"), "-o", lib,
-                        os.path.join(csrc, "srbd_mpc.hip")], check=True)
+        build_variant(lib, flags.split(), regn=needs_regn(HORIZON), csrc=csrc or None)
         env = {**os.environ, "SRBD_LIB": lib}
         cmd = [sys.executable, os.path.join(ROOT, "scripts/kernel_ab.py"), HORIZON, "4096", "10", "auto"]
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)

@@ -1,17 +1,15 @@
-"""Diagnostic: build compile-time variants of libsrbd_mpc.so into /tmp and compare their parity
-with the oracle (run on the GPU box). Usage: python scripts/variant_parity.py NAME=-DFLAG ..."""
+"""Diagnostic: build compile-time variants of libsrbd_mpc.so into /tmp (scripts/build_variant.py; the
+horizons below are 10 and 20, so without the srbd_regN.hip unit) and compare their parity with the
+oracle (run on the GPU box). Usage: python scripts/variant_parity.py NAME=-DFLAG[,-DFLAG] ..."""
 import os
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from build_variant import ROOT, build_variant
+
 variants = [a.split("=", 1) for a in sys.argv[1:]] or [["base", ""]]
 for name, flags in variants:
-    out = f"/tmp/libsrbd_{name}.so"
-    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-                    *[f for f in flags.split(",") if f], "-o", out,
-                    os.path.join(ROOT, "biped_pympc_amd/csrc/srbd_mpc.hip")], check=True)
+    build_variant(f"/tmp/libsrbd_{name}.so", [f for f in flags.split(",") if f], regn=False)
 code = r'''
 import sys, numpy as np, torch
 sys.path.insert(0, %r)

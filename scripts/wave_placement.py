@@ -5,15 +5,12 @@ python scripts/wave_placement.py [B]      (GPU box; builds /tmp/libsrbd_mpc_hwid
 """
 import collections
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-lib = "/tmp/libsrbd_mpc_hwid.so"
-subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-                "-DSRBD_HWID_DUMP", *os.environ.get("WP_FLAGS", "").split(), "-I", os.path.join(ROOT, "include"), "-o", lib,
-                os.path.join(ROOT, "biped_pympc_amd/csrc/srbd_mpc.hip")], check=True)
+from build_variant import build_variant
+
+lib = "/tmp/libsrbd_mpc_hwid.so"  # N = 10 below: built without the srbd_regN.hip unit
+build_variant(lib, ["-DSRBD_HWID_DUMP", *os.environ.get("WP_FLAGS", "").split()], regn=False)
 os.environ["SRBD_LIB"] = lib
 import numpy as np  # noqa: E402
 import torch  # noqa: E402

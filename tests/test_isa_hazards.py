@@ -11,7 +11,6 @@ checker). Where hipcc exists the audit must run: it fails rather than skips.
 """
 import os
 import shutil
-import subprocess
 import sys
 
 import pytest
@@ -20,26 +19,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
 
 
-REGN_PARTS = 6  # csrc/srbd_regN.hip SRBD_REGN_PART: its horizons in six parts, compiled in parallel
-
-
 def _isa(tmp_path, unit):
-    """Device ISA of one translation unit: a list of .s files (srbd_regN.hip: one per horizon part,
-    the parts compiled concurrently with the product flags plus -DSRBD_REGN_PART=k)."""
-    from biped_pympc_amd.build import HIPCC, unit_compile_cmd
+    """Device ISA of one translation unit: a list of .s files (srbd_regN.hip: one per horizon part),
+    listed by the product build's own recipe (build.py isa_listings)."""
+    from biped_pympc_amd.build import HIPCC, isa_listings
     if not (os.path.exists(HIPCC) or shutil.which("hipcc")):
         pytest.skip("hipcc not available")
-    parts = [[f"-DSRBD_REGN_PART={k}"] for k in range(REGN_PARTS)] if unit == "srbd_regN.hip" else [[]]
-    outs, procs = [], []
-    for k, defs in enumerate(parts):
-        out = tmp_path / f"{unit}.{k}.s"
-        cmd = unit_compile_cmd(unit, [*defs, "--cuda-device-only", "-S", "-o", str(out)])
-        procs.append(subprocess.Popen(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True))
-        outs.append(str(out))
-    for p in procs:
-        err = p.communicate()[1]
-        assert p.returncode == 0, err[-2000:]
-    return outs
+    return isa_listings(str(tmp_path), [unit])[unit]
 
 
 def _reg_horizon(name):
