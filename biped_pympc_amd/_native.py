@@ -132,6 +132,19 @@ def lib() -> ctypes.CDLL:
     L.srbd_mpc_backward_workspace_doubles.argtypes = [ctypes.c_int, ctypes.c_int]
     L.srbd_mpc_backward.restype = ctypes.c_int
     L.srbd_mpc_backward.argtypes = [ctypes.c_int, ctypes.c_int, P, P, _c_dp, _c_dp, P, _c_dp, ctypes.c_void_p]
+    # several seeds at one iterate (one factorisation, M solves): Jacobians and the u0 feedback gain
+    L.srbd_pdipm_backward_multi.restype = ctypes.c_int
+    L.srbd_pdipm_backward_multi.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, P, _c_dp, ctypes.c_size_t, P,
+                                            _c_dp, ctypes.c_void_p]
+    L.srbd_qp_former_backward_multi.restype = ctypes.c_int
+    L.srbd_qp_former_backward_multi.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, P, P, P, ctypes.c_void_p]
+    L.srbd_former_grad_deps.restype = ctypes.c_uint
+    L.srbd_former_grad_deps.argtypes = [ctypes.c_int]
+    L.srbd_mpc_backward_multi_workspace_doubles.restype = ctypes.c_size_t
+    L.srbd_mpc_backward_multi_workspace_doubles.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint]
+    L.srbd_mpc_backward_multi.restype = ctypes.c_int
+    L.srbd_mpc_backward_multi.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, P, P, _c_dp, ctypes.c_size_t,
+                                          _c_dp, P, _c_dp, ctypes.c_void_p]
     _lib = L
     return L
 

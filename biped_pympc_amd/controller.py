@@ -291,6 +291,18 @@ class MPCControllerHIP(BaseMPCController):
         self._step(self._prep_struct(keep), None, None)
         return self.foot_wrench, self.cost
 
+    def feedback_gain(self) -> torch.Tensor:
+        """The first-order feedback gain of the last step, K = d u0 / d x0 (B, 12, 12) float64 in the QP's
+        own coordinates (solver.mpc_feedback_gain): the MPC runs every `decimation` control ticks, and with K
+        the caller can apply u ~ u0 + K (x - x0) in between. Computed from ``self.former_inputs`` and
+        ``self.solution[:4]``, which a step writes only with ``cfg.keep_solution``. K is the derivative of
+        the linearised KKT conditions at the returned iterate: exact at convergence."""
+        if not self.cfg.keep_solution or getattr(self, "solution", None) is None:
+            raise RuntimeError("MPCControllerHIP.feedback_gain() needs cfg.keep_solution=True and a step run "
+                               "with it: without it the step writes neither the former inputs nor the "
+                               "solution the gain is linearised at")
+        return solver.mpc_feedback_gain(self.former_inputs, list(self.solution[:4]), self.horizon_length)
+
     def run_three_kernel(self, J: torch.Tensor | None = None, cb: torch.Tensor | None = None):
         """The same step as three launches (srbd_prepare_inputs -> srbd_mpc_solve_fused ->
         srbd_u0_wrench_torque) with the 17 former inputs and the solution in device memory.

@@ -220,10 +220,177 @@ __global__ __launch_bounds__(64) void pdipm_backward_kernel(BackwardArgs args) {
   }
 }
 
+// ---- several seeds at one iterate ----
+// K depends on the QP and the iterate only, so M seeds g_0 .. g_{M-1} at the same iterate share the
+// compact load, the stage-invariance check, constants() and factor(); only the solve, the refinement
+// step and the gradient epilogue run per seed. factor()'s results (WD, DI, PH, DV) are read-only to
+// solve() and refine_rhs() -- the forward kernel already runs two solves and two refinement solves per
+// factorisation -- so seed k's outputs have the bits pdipm_backward_kernel<0> gives for g_k alone.
+// Seed k of env e is read at grad_x + e * env_stride + k * 24N: env_stride = 0 shares one (M, 24N)
+// block among all envs (unit seeds: a Jacobian's rows), env_stride = M * 24N is a (B, M, 24N) tensor.
+// Output o's row of (env e, seed k) is e * M + k. A QP that is not stage-invariant gets NaN in its M
+// rows; kStatusNonFinite reports a non-finite adjoint of any of the M seeds.
+struct BackwardMultiArgs {
+  const double* in[10];  // as BackwardArgs
+  const double* grad_x;  // seeds, addressed as above
+  size_t env_stride;     // 0 or n_seeds * 24N (doubles)
+  double* out[6];        // (B, M, width) each; null: not written
+  int* status;           // (B) or null
+  int N;
+  int batch;
+  int n_seeds;           // M >= 1
+};
+
+template <int NT>  // 0 = horizon at run time (the only instantiation, srbd_backward.hip)
+__global__ __launch_bounds__(64) void pdipm_backward_multi_kernel(BackwardMultiArgs args) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int env = xcd_item(blockIdx.x, gridDim.x);
+  if (env >= args.batch) return;
+  const int N = NT > 0 ? NT : args.N, lane = threadIdx.x, M = args.n_seeds;
+  const BackwardLayout Lo(N);
+  FastCtx<NT> C;
+  C.N_ = N;
+  C.lane = lane;
+  C.bind(smem, Lo.base);
+  C.fg = C.hg = C.bg = nullptr;  // residuals() is never called: f, h, b are not read
+  C.xsg = smem + Lo.XS;
+  C.ysg = smem + Lo.YS;
+  const int nz = 24 * N, m = 16 * N, p = 14 * N, nA = nnz_A(N), nG = 28 * N;
+  const int width[6] = {nz, nz, nA, p, nG, m};
+  const double* Hg = args.in[0] + (size_t)env * nz;
+  const double* Gg = args.in[1] + (size_t)env * nG;
+  const double* Ag = args.in[2] + (size_t)env * nA;
+  const size_t row0 = (size_t)env * (size_t)M;  // this env's first output row
+
+  // ---- compact load and the stage-invariance check, as pdipm_backward_kernel ----
+  for (int e = lane; e < 144; e += 64) {
+    const int r = e / 12, j = e % 12;
+    const int om = c_tab.Mi[r][j], on = c_tab.Ni[r][j];
+    C.Md[e] = (N >= 2 && om >= 0) ? Ag[a_xblock(1) + om] : 0.0;
+    C.Nd[e] = on >= 0 ? Ag[a_ublock(N, 0) + on] : 0.0;
+  }
+  for (int e = lane; e < 192; e += 64) C.Gd[e] = 0.0;
+  if (lane < 12) {
+    C.Pd[lane] = Ag[a_pidx(c_tab, N, 0, lane)];
+    C.Hu[lane] = Hg[12 * N + lane];
+    C.Hu[12 + lane] = Hg[lane];
+  }
+  __syncthreads();
+  if (lane < 28) C.Gd[c_tab.grow[lane] * 12 + c_tab.gcol[lane]] = Gg[lane];
+  bool bad = false;
+  for (int e = lane; e < nA; e += 64) {
+    int ref;
+    if (e < 36 * (N - 1)) ref = e % 36;
+    else if (e < a_ubase(N)) ref = a_pidx(c_tab, N, 0, e - 36 * (N - 1));
+    else ref = a_ubase(N) + (e - a_ubase(N)) % 86;
+    bad |= !(Ag[e] == Ag[ref]);
+  }
+  for (int e = lane; e < nG; e += 64) bad |= !(Gg[e] == Gg[e % 28]);
+  for (int e = lane; e < nz; e += 64) bad |= !(Hg[e] == Hg[(e < 12 * N ? 0 : 12 * N) + e % 12]);
+  if (__any(bad)) {  // not differentiated: NaN in all M rows of every requested output
+    const double qnan = __builtin_nan("");
+#pragma unroll
+    for (int o = 0; o < 6; ++o) {
+      if (!args.out[o]) continue;
+      double* dst = args.out[o] + row0 * (size_t)width[o];
+      const size_t n = (size_t)M * (size_t)width[o];
+      for (size_t e = lane; e < n; e += 64) dst[e] = qnan;
+    }
+    if (args.status && lane == 0) args.status[env] = kStatusUnsupported;
+    return;
+  }
+  C.constants(Ag[a_ubase(N) + c_tab.e6], Ag[a_ubase(N) + c_tab.e9]);
+
+  // ---- the iterate and its factorisation, once ----
+  {
+    const double* xg = args.in[6] + (size_t)env * nz;
+    const double* sg = args.in[7] + (size_t)env * m;
+    const double* zg = args.in[8] + (size_t)env * m;
+    const double* yg = args.in[9] + (size_t)env * p;
+    for (int e = lane; e < nz; e += 64) C.X[e] = xg[e];
+    for (int e = lane; e < m; e += 64) {
+      C.S[e] = sg[e];
+      C.Z[e] = zg[e];
+    }
+    for (int e = lane; e < p; e += 64) C.Y[e] = yg[e];
+  }
+  __syncthreads();
+  C.factor();
+
+  const double* seeds = args.grad_x + (size_t)env * args.env_stride;
+  bool nf = false;
+#pragma unroll 1
+  for (int k = 0; k < M; ++k) {
+    // ---- seed k's right-hand side [g_k; 0; 0; 0]: every array the solve, the refinement and the
+    // epilogue read is written here or by this seed's own solve (refine_rhs overwrites RX and RE,
+    // solve(2) leaves its correction in VV, xsg / ysg are rewritten by refine_rhs) ----
+    const double* gg = seeds + (size_t)k * nz;
+    for (int e = lane; e < nz; e += 64) C.RX[e] = -gg[e];
+    for (int e = lane; e < m; e += 64) {
+      C.RS[e] = 0.0;
+      C.R2[e] = 0.0;
+      C.VV[e] = 0.0;
+    }
+    for (int e = lane; e < p; e += 64) C.RE[e] = 0.0;
+    __syncthreads();
+
+    // ---- one solve and one refinement step against the full K ----
+    C.solve(3, 0.0);
+    C.refine_rhs();
+    C.solve(2, 0.0);
+    // lx = TV, ls = DS, lz = DZ, ly = saved + correction
+    double* LY = C.ysg;
+    for (int e = lane; e < p; e += 64) LY[e] = LY[e] + C.DY[e];
+    __syncthreads();
+
+    // ---- gradients, row env * M + k ----
+    const size_t row = row0 + (size_t)k;
+    double* oH = args.out[0] ? args.out[0] + row * nz : nullptr;
+    double* of = args.out[1] ? args.out[1] + row * nz : nullptr;
+    double* oA = args.out[2] ? args.out[2] + row * nA : nullptr;
+    double* ob = args.out[3] ? args.out[3] + row * p : nullptr;
+    double* oG = args.out[4] ? args.out[4] + row * nG : nullptr;
+    double* od = args.out[5] ? args.out[5] + row * m : nullptr;
+    const double *lx = C.TV, *lz = C.DZ;
+    for (int e = lane; e < nz; e += 64) {
+      nf = nf || not_finite(lx[e]);
+      if (oH) oH[e] = grad_diag(lx[e], C.X[e]);
+      if (of) of[e] = -lx[e];
+    }
+    if (oA)
+      for (int e = lane; e < nA; e += 64) {
+        int r, c;
+        a_entry_rc(e, N, r, c);
+        oA[e] = grad_entry(lx[c], C.Y[r], LY[r], C.X[c]);
+      }
+    for (int e = lane; e < p; e += 64) {
+      nf = nf || not_finite(LY[e]);
+      if (ob) ob[e] = LY[e];
+    }
+    if (oG)
+      for (int e = lane; e < nG; e += 64) {
+        const int i = e / 28, q = e % 28;
+        const int r = 16 * i + c_tab.grow[q], c = 12 * N + 12 * i + c_tab.gcol[q];
+        oG[e] = grad_entry(lx[c], C.Z[r], lz[r], C.X[c]);
+      }
+    for (int e = lane; e < m; e += 64) {
+      nf = nf || not_finite(lz[e]);
+      if (od) od[e] = lz[e];
+    }
+    __syncthreads();  // the epilogue's reads of TV, DZ, LY before the next seed's right-hand side and solve
+  }
+  if (args.status) {
+    const bool any_nf = __any(nf);
+    if (lane == 0) args.status[env] = any_nf ? kStatusNonFinite : 0;
+  }
+}
+
 namespace bwd {
 // host side of the backward translation unit (srbd_backward.hip)
 const void* adjoint_kernel();
 void launch_adjoint(const BackwardArgs& a, size_t lds, hipStream_t s);
+const void* adjoint_multi_kernel();
+void launch_adjoint_multi(const BackwardMultiArgs& a, size_t lds, hipStream_t s);
 }  // namespace bwd
 
 }  // namespace srbd

@@ -14,9 +14,12 @@
 //   dt, m, R_body, I_world, body / foot positions, residual accelerations <- grad_A, grad_b through
 //                    A_d, B_d, c_d (R_body and I_world decoded column-major, as the former reads them)
 //   x, u          <- zero: the model is affine, the QP does not depend on the linearisation point
-// Mapping: one wavefront per env, four envs per workgroup, as the former; the env's model is
+// Mapping: one wavefront per gradient row, four rows per workgroup, as the former; the row's model is
 // recomputed by the former's own device code (former_model). Sums run in a fixed order per entry and
 // products are not contracted: an env's gradients do not depend on its position in the batch.
+// Seed rows (pdipm_backward.hpp, several seeds at one iterate): with n_seeds = M the gradients g[] and
+// out[] have batch * M rows and row r belongs to env r / M, whose former inputs it reads; M = 1 is one
+// row per env.
 #pragma once
 #include "qp_former.hpp"
 
@@ -28,6 +31,7 @@ struct FormerBackwardArgs {
   double* out[17];       // gradients of the former inputs; null: not written
   int N;
   int batch;
+  int n_seeds;           // M >= 1: g[] and out[] hold batch * M rows, row r of env r / M
 };
 
 struct FormerBackwardLds {
@@ -52,8 +56,9 @@ __global__ __launch_bounds__(64 * kWaves) void qp_former_backward_kernel(FormerB
   const Tables& tab = c_tab;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int env = xcd_item(blockIdx.x, gridDim.x) * kWaves + wave;
-  if (env >= args.batch) return;
+  const int row = xcd_item(blockIdx.x, gridDim.x) * kWaves + wave;
+  if (row >= args.batch * args.n_seeds) return;
+  const int env = row / args.n_seeds;
   const int N = args.N;
   FormerBackwardLds& W = lds[wave];
   FormerLds& L = W.F;
@@ -63,16 +68,16 @@ __global__ __launch_bounds__(64 * kWaves) void qp_former_backward_kernel(FormerB
 #pragma unroll
   for (int i = 0; i < 17; ++i) {
     P[i] = args.in[i] + (size_t)env * in_nnz[i];
-    O[i] = args.out[i] ? args.out[i] + (size_t)env * in_nnz[i] : nullptr;
+    O[i] = args.out[i] ? args.out[i] + (size_t)row * in_nnz[i] : nullptr;
   }
   former_model(L, P, lane);
   const double dt = P[4][0], mass = P[5][0], h2 = 0.5 * dt * dt;
-  const double* gH = args.g[0] ? args.g[0] + (size_t)env * (24 * N) : nullptr;
-  const double* gf = args.g[1] ? args.g[1] + (size_t)env * (24 * N) : nullptr;
-  const double* gA = args.g[2] ? args.g[2] + (size_t)env * nnz_A(N) : nullptr;
-  const double* gb = args.g[3] ? args.g[3] + (size_t)env * (14 * N) : nullptr;
-  const double* gG = args.g[4] ? args.g[4] + (size_t)env * (28 * N) : nullptr;
-  const double* gd = args.g[5] ? args.g[5] + (size_t)env * (16 * N) : nullptr;
+  const double* gH = args.g[0] ? args.g[0] + (size_t)row * (24 * N) : nullptr;
+  const double* gf = args.g[1] ? args.g[1] + (size_t)row * (24 * N) : nullptr;
+  const double* gA = args.g[2] ? args.g[2] + (size_t)row * nnz_A(N) : nullptr;
+  const double* gb = args.g[3] ? args.g[3] + (size_t)row * (14 * N) : nullptr;
+  const double* gG = args.g[4] ? args.g[4] + (size_t)row * (28 * N) : nullptr;
+  const double* gd = args.g[5] ? args.g[5] + (size_t)row * (16 * N) : nullptr;
   const double* Qw = P[13];
   const double* xr = P[3];
 

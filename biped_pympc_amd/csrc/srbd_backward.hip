@@ -17,8 +17,15 @@ void launch_adjoint(const BackwardArgs& a, size_t lds, hipStream_t s) {
   hipLaunchKernelGGL(pdipm_backward_kernel<0>, dim3(a.batch), dim3(64), lds, s, a);
 }
 
+const void* adjoint_multi_kernel() { return (const void*)pdipm_backward_multi_kernel<0>; }
+
+void launch_adjoint_multi(const BackwardMultiArgs& a, size_t lds, hipStream_t s) {
+  hipLaunchKernelGGL(pdipm_backward_multi_kernel<0>, dim3(a.batch), dim3(64), lds, s, a);
+}
+
 void launch_former_backward(const FormerBackwardArgs& a, hipStream_t s) {
-  const int grid = (a.batch + kFormerWaves - 1) / kFormerWaves;
+  const int rows = a.batch * a.n_seeds;  // the host entry checks that it fits an int
+  const int grid = (rows + kFormerWaves - 1) / kFormerWaves;
   hipLaunchKernelGGL(qp_former_backward_kernel<kFormerWaves>, dim3(grid), dim3(64 * kFormerWaves), 0, s, a);
 }
 

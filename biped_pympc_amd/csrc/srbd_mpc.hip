@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -759,6 +760,7 @@ int srbd_qp_former_backward(int horizon, int batch, const double* const* former_
   for (int i = 0; i < 6; ++i) a.g[i] = qp_grads[i];  // null: a zero gradient
   a.N = horizon;
   a.batch = batch;
+  a.n_seeds = 1;
   srbd::bwd::launch_former_backward(a, (hipStream_t)stream);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : set_error((int)e, "qp_former_backward_kernel launch");
@@ -789,6 +791,159 @@ int srbd_mpc_backward(int horizon, int batch, const double* const* former_inputs
   const double* sin[10] = {qp[0], qp[4], qp[2], qp[1], qp[5], qp[3], iterate[0], iterate[1], iterate[2], iterate[3]};
   if (int rc = srbd_pdipm_backward(horizon, batch, sin, grad_x, gr, status, stream)) return rc;
   return srbd_qp_former_backward(horizon, batch, former_inputs, gr, input_grads, stream);
+}
+
+// ---- several seeds at one iterate (pdipm_backward.hpp: one factorisation, M solves) ----
+
+namespace {
+
+// batch * n_seeds gradient rows must fit the launch grid's int
+bool seed_rows_ok(int batch, int n_seeds) { return (long long)batch * (long long)n_seeds <= (long long)INT_MAX; }
+
+// the QP gradients (bit o: H, f, A, b, G, d) the gradient of former input i reads: the table in the
+// header comment of qp_former_backward.hpp
+constexpr unsigned kGradH = 1u, kGradF = 2u, kGradA = 4u, kGradB = 8u, kGradG = 16u, kGradD = 32u;
+constexpr unsigned kFormerGradDeps[17] = {
+    kGradB,           // x0
+    0u,               // x: zero gradient
+    0u,               // u: zero gradient
+    kGradF,           // x_ref
+    kGradA | kGradB,  // dt
+    kGradA | kGradB,  // m
+    kGradG,           // mu
+    kGradA | kGradB,  // R_body
+    kGradA | kGradB,  // I_world
+    kGradA | kGradB,  // body position
+    kGradA | kGradB,  // left foot position
+    kGradA | kGradB,  // right foot position
+    kGradD,           // contact_table
+    kGradH | kGradF,  // Q
+    kGradH,           // R
+    kGradA | kGradB,  // residual linear acceleration
+    kGradA | kGradB,  // residual angular acceleration
+};
+
+// the union of the dependencies of the inputs in input_mask (bit i = former input i; 0 = all 17)
+unsigned qp_grads_needed(unsigned input_mask) {
+  unsigned need = 0;
+  for (int i = 0; i < 17; ++i)
+    if (input_mask == 0 || (input_mask >> i & 1u)) need |= kFormerGradDeps[i];
+  return need;
+}
+
+void qp_widths(int horizon, size_t (&w)[6]) {  // H, f, A, b, G, d
+  const size_t N = (size_t)horizon;
+  w[0] = w[1] = 24 * N;
+  w[2] = 122 * N - 24;
+  w[3] = 14 * N;
+  w[4] = 28 * N;
+  w[5] = 16 * N;
+}
+
+}  // namespace
+
+int srbd_pdipm_backward_multi(int horizon, int batch, int n_seeds, const double* const* inputs,
+                              const double* grad_x, size_t grad_x_env_stride, double* const* qp_grads,
+                              int* status, void* stream) {
+  if (!horizon_ok(horizon) || batch < 0 || n_seeds < 1 || !inputs || !qp_grads)
+    return set_error(kErrInvalid, "srbd_pdipm_backward_multi: bad arguments");
+  if (grad_x_env_stride != 0 && grad_x_env_stride != (size_t)n_seeds * 24 * (size_t)horizon)
+    return set_error(kErrInvalid, "srbd_pdipm_backward_multi: grad_x_env_stride must be 0 or n_seeds * 24 * horizon");
+  if (!seed_rows_ok(batch, n_seeds))
+    return set_error(kErrInvalid, "srbd_pdipm_backward_multi: batch * n_seeds overflows");
+  if (batch == 0) return 0;
+  srbd::BackwardMultiArgs a{};
+  for (int i = 0; i < 10; ++i) {
+    if (!inputs[i] && !(i >= 3 && i <= 5)) return set_error(kErrInvalid, "srbd_pdipm_backward_multi: null input");
+    a.in[i] = inputs[i];  // f, h, b (3..5) are not read
+  }
+  if (!grad_x) return set_error(kErrInvalid, "srbd_pdipm_backward_multi: null grad_x");
+  a.grad_x = grad_x;
+  a.env_stride = grad_x_env_stride;
+  for (int i = 0; i < 6; ++i) a.out[i] = qp_grads[i];  // null: not written
+  a.status = status;
+  a.N = horizon;
+  a.batch = batch;
+  a.n_seeds = n_seeds;
+  static srbd::LdsAttr cfg_backward_multi;
+  const size_t lds = srbd::backward_lds_bytes(horizon);
+  if (lds > 160 * 1024) return set_error(kErrInvalid, "horizon too large for the LDS-resident backward solve");
+  if (int rc = ensure_lds_attr(srbd::bwd::adjoint_multi_kernel(), lds, cfg_backward_multi)) return rc;
+  srbd::bwd::launch_adjoint_multi(a, lds, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : set_error((int)e, "pdipm_backward_multi_kernel launch");
+}
+
+int srbd_qp_former_backward_multi(int horizon, int batch, int n_seeds, const double* const* former_inputs,
+                                  const double* const* qp_grads, double* const* input_grads, void* stream) {
+  if (!horizon_ok(horizon) || batch < 0 || n_seeds < 1 || !former_inputs || !qp_grads || !input_grads)
+    return set_error(kErrInvalid, "srbd_qp_former_backward_multi: bad arguments");
+  if (!seed_rows_ok(batch, n_seeds))
+    return set_error(kErrInvalid, "srbd_qp_former_backward_multi: batch * n_seeds overflows");
+  if (batch == 0) return 0;
+  srbd::FormerBackwardArgs a{};
+  for (int i = 0; i < 17; ++i) {
+    if (!former_inputs[i]) return set_error(kErrInvalid, "srbd_qp_former_backward_multi: null input");
+    a.in[i] = former_inputs[i];
+    a.out[i] = input_grads[i];  // null: not written
+  }
+  for (int i = 0; i < 6; ++i) a.g[i] = qp_grads[i];  // null: a zero gradient
+  a.N = horizon;
+  a.batch = batch;
+  a.n_seeds = n_seeds;
+  srbd::bwd::launch_former_backward(a, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : set_error((int)e, "qp_former_backward_kernel launch");
+}
+
+unsigned srbd_former_grad_deps(int input) { return input >= 0 && input < 17 ? kFormerGradDeps[input] : 0u; }
+
+size_t srbd_mpc_backward_multi_workspace_doubles(int horizon, int batch, int n_seeds, unsigned input_mask) {
+  if (!horizon_ok(horizon) || batch < 0 || n_seeds < 1 || !seed_rows_ok(batch, n_seeds)) return 0;
+  size_t w[6];
+  qp_widths(horizon, w);
+  const unsigned need = qp_grads_needed(input_mask);
+  size_t per_env = 0;
+  for (int o = 0; o < 6; ++o) per_env += w[o] + ((need >> o & 1u) ? (size_t)n_seeds * w[o] : 0);
+  return (size_t)batch * per_env;  // the QP, then the needed gradients, (B, M, width) each
+}
+
+int srbd_mpc_backward_multi(int horizon, int batch, int n_seeds, const double* const* former_inputs,
+                            const double* const* iterate, const double* grad_x, size_t grad_x_env_stride,
+                            double* workspace, double* const* input_grads, int* status, void* stream) {
+  if (!horizon_ok(horizon) || batch < 0 || n_seeds < 1 || !former_inputs || !iterate || !input_grads)
+    return set_error(kErrInvalid, "srbd_mpc_backward_multi: bad arguments");
+  if (grad_x_env_stride != 0 && grad_x_env_stride != (size_t)n_seeds * 24 * (size_t)horizon)
+    return set_error(kErrInvalid, "srbd_mpc_backward_multi: grad_x_env_stride must be 0 or n_seeds * 24 * horizon");
+  if (!seed_rows_ok(batch, n_seeds))
+    return set_error(kErrInvalid, "srbd_mpc_backward_multi: batch * n_seeds overflows");
+  if (batch == 0) return 0;
+  if (!workspace || !grad_x || !iterate[0] || !iterate[1] || !iterate[2] || !iterate[3])
+    return set_error(kErrInvalid, "srbd_mpc_backward_multi: null workspace / grad_x / iterate");
+  unsigned input_mask = 0;
+  for (int i = 0; i < 17; ++i)
+    if (input_grads[i]) input_mask |= 1u << i;
+  if (input_mask == 0) return set_error(kErrInvalid, "srbd_mpc_backward_multi: no input gradient requested");
+  const unsigned need = qp_grads_needed(input_mask);
+  const size_t B = (size_t)batch, M = (size_t)n_seeds;
+  size_t w[6];
+  qp_widths(horizon, w);
+  double* qp[6];
+  double* gr[6];
+  double* o = workspace;
+  for (int i = 0; i < 6; ++i) {
+    qp[i] = o;
+    o += B * w[i];
+  }
+  for (int i = 0; i < 6; ++i) {  // only the gradients the requested inputs read; the others stay NULL
+    gr[i] = (need >> i & 1u) ? o : nullptr;
+    if (gr[i]) o += B * M * w[i];
+  }
+  if (int rc = srbd_qp_former(horizon, batch, former_inputs, qp, stream)) return rc;
+  const double* sin[10] = {qp[0], qp[4], qp[2], qp[1], qp[5], qp[3], iterate[0], iterate[1], iterate[2], iterate[3]};
+  if (int rc = srbd_pdipm_backward_multi(horizon, batch, n_seeds, sin, grad_x, grad_x_env_stride, gr, status, stream))
+    return rc;
+  return srbd_qp_former_backward_multi(horizon, batch, n_seeds, former_inputs, gr, input_grads, stream);
 }
 
 int srbd_pattern_ccs(int horizon, int which, int* colptr, int* rowind) {

@@ -309,6 +309,177 @@ def mpc_backward(former_inputs: list[torch.Tensor], iterate: list[torch.Tensor],
     return outs
 
 
+# ---- several seeds at one iterate: solution Jacobians and the u0 feedback gain ----
+# The KKT matrix of the adjoint system depends on the QP and the iterate only, so M seeds share one
+# factorisation (srbd_pdipm_backward_multi). Everything below is the derivative of the linearised KKT
+# conditions at the iterate: exact at convergence, and at a non-converged iterate the
+# derivative of the Newton step's linear system, as the single-seed entries above.
+
+def _seed_block(grad_x: torch.Tensor, B: int, N: int, what: str):
+    """grad_x (M, 24N), shared by every env, or (B, M, 24N), per env -> (M, the C-ABI's env stride)."""
+    nz = 24 * N
+    if not isinstance(grad_x, torch.Tensor) or not grad_x.is_cuda or grad_x.dtype != torch.float64:
+        raise TypeError(f"{what}: grad_x must be a CUDA float64 tensor")
+    if grad_x.device.index != torch.cuda.current_device():
+        raise ValueError(f"{what}: grad_x is on {grad_x.device}, the current device is cuda:{torch.cuda.current_device()}")
+    if not grad_x.is_contiguous():
+        raise ValueError(f"{what}: grad_x must be contiguous")
+    if grad_x.dim() == 2 and grad_x.shape[1] == nz and grad_x.shape[0] >= 1:
+        return grad_x.shape[0], 0
+    if grad_x.dim() == 3 and grad_x.shape[0] == B and grad_x.shape[2] == nz and grad_x.shape[1] >= 1:
+        return grad_x.shape[1], grad_x.shape[1] * nz
+    raise ValueError(f"{what}: grad_x must be (M, {nz}) (shared by every env) or ({B}, M, {nz}), M >= 1, "
+                     f"got {tuple(grad_x.shape)}")
+
+
+def _seed_outputs(outputs, widths, B: int, M: int, device, what: str, want=None):
+    """(B, M, width) outputs: None -> those in `want` (default all) allocated; a list -> its tensors,
+    None entries stay unwritten (NULL)."""
+    if outputs is None:
+        outputs = [torch.empty((B, M, w), dtype=torch.float64, device=device) if want is None or i in want else None
+                   for i, w in enumerate(widths)]
+    _check_batch(outputs, [M * w for w in widths], B, what)
+    return list(outputs)
+
+
+def pdipm_backward_multi(qp: list, iterate: list[torch.Tensor], grad_x: torch.Tensor, N: int,
+                         status: torch.Tensor | None = None, outputs: list | None = None):
+    """``pdipm_backward`` for M seeds at one iterate with one factorisation and M solves.
+
+    ``grad_x`` of shape (M, 24N) is shared by every env (unit seeds: no (B, M, 24N) tensor is needed);
+    (B, M, 24N) is per env. Returns [grad_H, grad_f, grad_A, grad_b, grad_G, grad_d], each (B, M, width);
+    row [b, k] has the bits ``pdipm_backward`` returns for env b and seed k alone. ``outputs``:
+    preallocated (B, M, width) tensors, None entries are skipped. ``status`` (int32 (B,), optional):
+    STATUS_UNSUPPORTED for a QP that is not stage-invariant (all its M rows are NaN), STATUS_NONFINITE
+    when the adjoint of any of its seeds is non-finite. The result is the derivative of the linearised
+    KKT conditions at the iterate: exact at convergence."""
+    d = Dims(N)
+    B = iterate[0].shape[0]
+    ins = list(qp) + list(iterate)
+    _check_batch(ins, d.solver_in_nnz, B, "pdipm_backward_multi")
+    if any(ins[i] is None for i in (0, 1, 2, 6, 7, 8, 9)):
+        raise ValueError("pdipm_backward_multi: Q_val, G_val, A_val and the iterate x, s, z, y are required")
+    M, stride = _seed_block(grad_x, B, N, "pdipm_backward_multi")
+    outs = _seed_outputs(outputs, d.former_out_nnz, B, M, grad_x.device, "pdipm_backward_multi outputs")
+    st = _check_status(status, B, "pdipm_backward_multi")
+    rc = _native.lib().srbd_pdipm_backward_multi(N, B, M, _ptrs(ins), grad_x.data_ptr(), stride, _ptrs(outs), st,
+                                                 _stream_ptr())
+    _native.check(rc, "srbd_pdipm_backward_multi")
+    return outs
+
+
+def qp_former_backward_multi(former_inputs: list[torch.Tensor], qp_grads: list, N: int, outputs: list | None = None):
+    """``qp_former_backward`` over seed rows: ``qp_grads`` = six (B, M, width) tensors (None: a zero
+    gradient, at least one given) -> the gradients of the 17 former inputs, each (B, M, width); row
+    [b, k] uses env b's former inputs and has the bits of the single-seed call on that row.
+    ``outputs``: preallocated tensors, None entries are skipped."""
+    d = Dims(N)
+    B = former_inputs[0].shape[0]
+    _check_batch(former_inputs, d.former_in_nnz, B, "qp_former_backward_multi")
+    given = [(g, w) for g, w in zip(qp_grads, d.former_out_nnz) if g is not None]
+    if not given:
+        raise ValueError("qp_former_backward_multi: at least one QP gradient is needed (it carries the seed count)")
+    g0, w0 = given[0]
+    if g0.dim() != 3 or g0.shape[0] != B or g0.shape[2] != w0 or g0.shape[1] < 1:
+        raise ValueError(f"qp_former_backward_multi: gradients must be ({B}, M, width), got {tuple(g0.shape)}")
+    M = g0.shape[1]
+    _check_batch(qp_grads, [M * w for w in d.former_out_nnz], B, "qp_former_backward_multi gradients")
+    outs = _seed_outputs(outputs, d.former_in_nnz, B, M, former_inputs[0].device, "qp_former_backward_multi outputs")
+    rc = _native.lib().srbd_qp_former_backward_multi(N, B, M, _ptrs(former_inputs), _ptrs(qp_grads), _ptrs(outs),
+                                                     _stream_ptr())
+    _native.check(rc, "srbd_qp_former_backward_multi")
+    return outs
+
+
+def _input_mask(wrt) -> int:
+    mask = 0
+    for i in wrt:
+        if not 0 <= int(i) < 17:
+            raise ValueError(f"wrt: former-input index {i} outside 0..16")
+        mask |= 1 << int(i)
+    return mask
+
+
+def mpc_backward_multi(former_inputs: list[torch.Tensor], iterate: list[torch.Tensor], grad_x: torch.Tensor, N: int,
+                       wrt=None, status: torch.Tensor | None = None, outputs: list | None = None,
+                       workspace: torch.Tensor | None = None):
+    """``srbd_mpc_backward_multi``: qp_former (once per env) -> pdipm_backward_multi -> qp_former_backward_multi
+    in one call (same bits), for the M seeds ``grad_x`` ((M, 24N) shared, or (B, M, 24N)).
+
+    ``wrt``: the former-input indices wanted (None: all 17). Returns a list of 17 with (B, M, width)
+    gradients at those indices and None elsewhere: the others are neither computed nor allocated, and
+    only the QP gradients the wanted inputs read are held in the workspace
+    (``srbd_mpc_backward_multi_workspace_doubles``). ``outputs``: preallocated tensors instead (None
+    entries are skipped; ``wrt`` is then taken from it). The result is the derivative of the linearised
+    KKT conditions at the iterate: exact at convergence."""
+    d = Dims(N)
+    B = former_inputs[0].shape[0]
+    _check_batch(former_inputs, d.former_in_nnz, B, "mpc_backward_multi")
+    _check_batch(list(iterate), d.solver_in_nnz[6:], B, "mpc_backward_multi iterate")
+    M, stride = _seed_block(grad_x, B, N, "mpc_backward_multi")
+    if outputs is not None:
+        wrt = [i for i, t in enumerate(outputs) if t is not None]
+    want = set(range(17)) if wrt is None else {int(i) for i in wrt}
+    mask = _input_mask(want)
+    if mask == 0:
+        raise ValueError("mpc_backward_multi: no former input requested")
+    outs = _seed_outputs(outputs, d.former_in_nnz, B, M, grad_x.device, "mpc_backward_multi outputs", want)
+    L = _native.lib()
+    n = L.srbd_mpc_backward_multi_workspace_doubles(N, B, M, mask)
+    if workspace is None:
+        workspace = torch.empty(max(n, 1), dtype=torch.float64, device=grad_x.device)
+    if not workspace.is_cuda or workspace.dtype != torch.float64 or workspace.numel() < n or not workspace.is_contiguous():
+        raise ValueError(f"mpc_backward_multi: workspace must be a contiguous CUDA float64 tensor of >= {n} elements")
+    st = _check_status(status, B, "mpc_backward_multi")
+    rc = L.srbd_mpc_backward_multi(N, B, M, _ptrs(former_inputs), _ptrs(iterate), grad_x.data_ptr(), stride,
+                                   workspace.data_ptr(), _ptrs(outs), st, _stream_ptr())
+    _native.check(rc, "srbd_mpc_backward_multi")
+    return outs
+
+
+def unit_seeds(N: int, rows, device="cuda") -> torch.Tensor:
+    """(len(rows), 24N) float64: the unit vectors of x at the indices ``rows`` (seeds shared by every env)."""
+    rows = [int(r) for r in rows]
+    if not rows or any(not 0 <= r < 24 * N for r in rows):
+        raise ValueError(f"rows: at least one index into x, each in 0..{24 * N - 1}")
+    g = torch.zeros((len(rows), 24 * N), dtype=torch.float64, device=device)
+    g[torch.arange(len(rows), device=device), torch.tensor(rows, device=device)] = 1.0
+    return g
+
+
+def mpc_jacobian(former_inputs: list[torch.Tensor], iterate: list[torch.Tensor], N: int, rows, wrt,
+                 status: torch.Tensor | None = None, seeds: torch.Tensor | None = None,
+                 outputs: list | None = None, workspace: torch.Tensor | None = None):
+    """Jacobians of solution components: for each former-input index in ``wrt``, (B, len(rows), width) =
+    d x[rows] / d input (a list of 17, None elsewhere). ``rows`` are indices into x (24N: the states
+    x_1..x_N, then the inputs u_0..u_{N-1}). One factorisation per env and len(rows) solves, with unit
+    seeds shared by every env (``seeds``: ``unit_seeds(N, rows)`` kept by the caller, e.g. for graph
+    capture). The Jacobian is that of the linearised KKT conditions at the iterate: exact
+    at convergence."""
+    if seeds is None:
+        seeds = unit_seeds(N, rows, former_inputs[0].device)
+    elif seeds.dim() != 2 or seeds.shape[0] != len(list(rows)):
+        raise ValueError("mpc_jacobian: seeds must be unit_seeds(N, rows)")
+    return mpc_backward_multi(former_inputs, iterate, seeds, N, wrt=wrt, status=status, outputs=outputs,
+                              workspace=workspace)
+
+
+def mpc_feedback_gain(former_inputs: list[torch.Tensor], iterate: list[torch.Tensor], N: int,
+                      status: torch.Tensor | None = None, seeds: torch.Tensor | None = None,
+                      out: torch.Tensor | None = None, workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """The first-order feedback gain K = d u0 / d x0, (B, 12, 12) with K[b, i, j] = d u0_i / d x0_j in the
+    QP's own coordinates: between two MPC solves the caller can apply u ~ u0 + K (x - x0) at the control
+    rate. Twelve unit seeds on the u0 block, one factorisation per env; only grad_b is materialised
+    (12 * 14N doubles per env next to the QP). K is the derivative of the linearised KKT conditions at the
+    iterate, so the gain is exact at convergence. ``seeds`` (``unit_seeds(N, range(12N,
+    12N + 12))``), ``out`` (B, 12, 12) and ``workspace`` may be preallocated (graph capture)."""
+    outs = [None] * 17
+    outs[0] = out if out is not None else torch.empty((former_inputs[0].shape[0], 12, 12), dtype=torch.float64,
+                                                      device=former_inputs[0].device)
+    return mpc_jacobian(former_inputs, iterate, N, range(12 * N, 12 * N + 12), [0], status=status, seeds=seeds,
+                        outputs=outs, workspace=workspace)[0]
+
+
 class _MPCSolveFunction(torch.autograd.Function):
     """x = mpc_solve(former_inputs): forward ``srbd_mpc_solve_fused``, backward ``srbd_mpc_backward`` on the
     saved iterate (the adjoint KKT solve and the former's vector-Jacobian product)."""

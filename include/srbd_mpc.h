@@ -363,6 +363,49 @@ int srbd_mpc_backward(int horizon, int batch, const double* const* former_inputs
                       const double* const* iterate /* x, s, z, y */, const double* grad_x,
                       double* workspace, double* const* input_grads, int* status, void* stream);
 
+/* ---- Several seeds at one iterate: solution Jacobians and the u0 feedback gain ----------------------
+ * K depends on the QP and the iterate only, so n_seeds = M seeds g_0 .. g_{M-1} on x share the load, the
+ * stage-invariance check and the factorisation: one factorisation and M solves (each with its refinement
+ * step) in one launch. Seed k's results have the bits srbd_pdipm_backward returns for g_k alone. The
+ * result is, as there, the derivative of the linearised KKT conditions at the iterate: exact at
+ * convergence. Conventions as the entry points above (host arrays of device pointers, asynchronous, no
+ * device allocation, batch == 0 returns 0 and bad arguments an error code without touching the GPU).
+ * Bad arguments: horizon outside 1..32, n_seeds < 1, a stride that is neither 0 nor n_seeds * 24N, a
+ * null required pointer, batch * n_seeds above INT_MAX. All row offsets are size_t.
+ *
+ * grad_x: seed k of env e at grad_x + e * grad_x_env_stride + k * 24N doubles. Stride 0: one (M, 24N)
+ * block shared by every env (unit seeds never need a (B, M, 24N) tensor); stride M * 24N: a (B, M, 24N)
+ * tensor. qp_grads: six outputs (B, M, width), row e * M + k, each skipped when NULL. A QP that is not
+ * stage-invariant gets NaN in its M rows and SRBD_STATUS_UNSUPPORTED; SRBD_STATUS_NONFINITE reports a
+ * non-finite adjoint of any of its seeds. status (B ints) may be NULL. */
+int srbd_pdipm_backward_multi(int horizon, int batch, int n_seeds, const double* const* inputs,
+                              const double* grad_x, size_t grad_x_env_stride /* 0 or n_seeds*24N */,
+                              double* const* qp_grads /* each (B, M, width) or NULL */, int* status, void* stream);
+
+/* srbd_qp_former_backward over seed rows: qp_grads and input_grads hold B * M rows, row r uses the
+ * former inputs of env r / M (former_inputs: B rows). n_seeds = 1 is srbd_qp_former_backward. */
+int srbd_qp_former_backward_multi(int horizon, int batch, int n_seeds, const double* const* former_inputs /* B rows */,
+                                  const double* const* qp_grads /* B*M rows, NULL = zero */,
+                                  double* const* input_grads /* B*M rows, NULL = skipped */, void* stream);
+
+/* Host-only: which QP gradients the gradient of former input `input` (0..16) reads, as a mask with bit
+ * 0..5 = grad_H, grad_f, grad_A, grad_b, grad_G, grad_d (0 for inputs 1 and 2, whose gradient is zero,
+ * and for an index out of range):
+ *   x0 <- b;  x_ref <- f;  Q <- H, f;  R <- H;  contact_table <- d;  mu <- G;
+ *   dt, m, R_body, I_world, the three positions, the two residual accelerations <- A, b. */
+unsigned srbd_former_grad_deps(int input);
+
+/* srbd_qp_former (once per env) -> srbd_pdipm_backward_multi -> srbd_qp_former_backward_multi in one call
+ * (same bits). Only the QP gradients that the requested inputs (non-NULL input_grads entries; at least
+ * one) read are materialised: the others are NULL to both kernels. workspace: the QP, then those
+ * gradients (B, M, width) -- srbd_mpc_backward_multi_workspace_doubles doubles, input_mask bit i = former
+ * input i requested (0 = all 17; 0 doubles for bad arguments). For the gain (x0 only) at N = 10, M = 12:
+ * the QP plus 12 * 140 doubles per env. */
+size_t srbd_mpc_backward_multi_workspace_doubles(int horizon, int batch, int n_seeds, unsigned input_mask /* 0 = all 17 */);
+int srbd_mpc_backward_multi(int horizon, int batch, int n_seeds, const double* const* former_inputs,
+                            const double* const* iterate, const double* grad_x, size_t grad_x_env_stride,
+                            double* workspace, double* const* input_grads, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
