@@ -720,85 +720,83 @@ int srbd_mpc_step(int horizon, int n_iter, int batch, double y0, const srbd_mpc_
 }
 
 // ---- backward pass (pdipm_backward.hpp, qp_former_backward.hpp; kernels in srbd_backward.hip) ----
+// One implementation per stage; the exported entries forward to them with their own name (`what`)
+// for the messages. A single-seed entry is n_seeds = 1 with the seeds' env stride 24 * horizon.
 
-int srbd_pdipm_backward(int horizon, int batch, const double* const* inputs, const double* grad_x,
-                        double* const* qp_grads, int* status, void* stream) {
-  if (!horizon_ok(horizon) || batch < 0 || !inputs || !qp_grads)
-    return set_error(kErrInvalid, "srbd_pdipm_backward: bad arguments");
-  if (batch == 0) return 0;
-  srbd::BackwardArgs a{};
-  for (int i = 0; i < 10; ++i) {
-    if (!inputs[i] && !(i >= 3 && i <= 5)) return set_error(kErrInvalid, "srbd_pdipm_backward: null input");
-    a.in[i] = inputs[i];  // f, h, b (3..5) are not read
-  }
-  if (!grad_x) return set_error(kErrInvalid, "srbd_pdipm_backward: null grad_x");
-  a.grad_x = grad_x;
-  for (int i = 0; i < 6; ++i) a.out[i] = qp_grads[i];  // null: not written
-  a.status = status;
-  a.N = horizon;
-  a.batch = batch;
-  static srbd::LdsAttr cfg_backward;
-  const size_t lds = srbd::backward_lds_bytes(horizon);
-  if (lds > 160 * 1024) return set_error(kErrInvalid, "horizon too large for the LDS-resident backward solve");
-  if (int rc = ensure_lds_attr(srbd::bwd::adjoint_kernel(), lds, cfg_backward)) return rc;
-  srbd::bwd::launch_adjoint(a, lds, (hipStream_t)stream);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : set_error((int)e, "pdipm_backward_kernel launch");
+namespace {
+
+int fail(const char* what, const char* msg) { return set_error(kErrInvalid, (std::string(what) + ": " + msg).c_str()); }
+
+// batch * n_seeds gradient rows must fit the launch grid's int
+bool seed_rows_ok(int batch, int n_seeds) { return (long long)batch * (long long)n_seeds <= (long long)INT_MAX; }
+
+// the checks every backward entry starts with
+int check_seeds(const char* what, int horizon, int batch, int n_seeds, size_t env_stride, bool pointers_ok) {
+  if (!horizon_ok(horizon) || batch < 0 || n_seeds < 1 || !pointers_ok) return fail(what, "bad arguments");
+  if (env_stride != 0 && env_stride != (size_t)n_seeds * 24 * (size_t)horizon)
+    return fail(what, "grad_x_env_stride must be 0 or n_seeds * 24 * horizon");
+  if (!seed_rows_ok(batch, n_seeds)) return fail(what, "batch * n_seeds overflows");
+  return 0;
 }
 
-int srbd_qp_former_backward(int horizon, int batch, const double* const* former_inputs,
-                            const double* const* qp_grads, double* const* input_grads, void* stream) {
-  if (!horizon_ok(horizon) || batch < 0 || !former_inputs || !qp_grads || !input_grads)
-    return set_error(kErrInvalid, "srbd_qp_former_backward: bad arguments");
+// the adjoint KKT solve and the QP-data gradients of n_seeds seeds per env
+int adjoint_impl(const char* what, int horizon, int batch, int n_seeds, const double* const* inputs,
+                 const double* grad_x, size_t env_stride, double* const* qp_grads, int* status, void* stream) {
+  if (int rc = check_seeds(what, horizon, batch, n_seeds, env_stride, inputs && qp_grads)) return rc;
+  if (batch == 0) return 0;
+  for (int i = 0; i < 10; ++i)
+    if (!inputs[i] && !(i >= 3 && i <= 5)) return fail(what, "null input");  // f, h, b (3..5) are not read
+  if (!grad_x) return fail(what, "null grad_x");
+  const size_t lds = srbd::backward_lds_bytes(horizon);
+  if (lds > 160 * 1024) return set_error(kErrInvalid, "horizon too large for the LDS-resident backward solve");
+  auto fill = [&](auto& a) {  // the fields BackwardArgs and BackwardMultiArgs share
+    for (int i = 0; i < 10; ++i) a.in[i] = inputs[i];
+    a.grad_x = grad_x;
+    for (int i = 0; i < 6; ++i) a.out[i] = qp_grads[i];  // null: not written
+    a.status = status;
+    a.N = horizon;
+    a.batch = batch;
+  };
+  // one seed per env, (B, 24N): the single-seed kernel (the other's bits, 1-2 % faster there)
+  if (n_seeds == 1 && env_stride != 0) {
+    static srbd::LdsAttr cfg_backward;
+    srbd::BackwardArgs a{};
+    fill(a);
+    if (int rc = ensure_lds_attr(srbd::bwd::adjoint_kernel(), lds, cfg_backward)) return rc;
+    srbd::bwd::launch_adjoint(a, lds, (hipStream_t)stream);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : set_error((int)e, "pdipm_backward_kernel launch");
+  }
+  static srbd::LdsAttr cfg_backward_multi;
+  srbd::BackwardMultiArgs a{};
+  fill(a);
+  a.env_stride = env_stride;
+  a.n_seeds = n_seeds;
+  if (int rc = ensure_lds_attr(srbd::bwd::adjoint_multi_kernel(), lds, cfg_backward_multi)) return rc;
+  srbd::bwd::launch_adjoint_multi(a, lds, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : set_error((int)e, "pdipm_backward_multi_kernel launch");
+}
+
+// the former's vector-Jacobian product over batch * n_seeds gradient rows
+int former_vjp_impl(const char* what, int horizon, int batch, int n_seeds, const double* const* former_inputs,
+                    const double* const* qp_grads, double* const* input_grads, void* stream) {
+  if (int rc = check_seeds(what, horizon, batch, n_seeds, 0, former_inputs && qp_grads && input_grads)) return rc;
   if (batch == 0) return 0;
   srbd::FormerBackwardArgs a{};
   for (int i = 0; i < 17; ++i) {
-    if (!former_inputs[i]) return set_error(kErrInvalid, "srbd_qp_former_backward: null input");
+    if (!former_inputs[i]) return fail(what, "null input");
     a.in[i] = former_inputs[i];
     a.out[i] = input_grads[i];  // null: not written
   }
   for (int i = 0; i < 6; ++i) a.g[i] = qp_grads[i];  // null: a zero gradient
   a.N = horizon;
   a.batch = batch;
-  a.n_seeds = 1;
+  a.n_seeds = n_seeds;
   srbd::bwd::launch_former_backward(a, (hipStream_t)stream);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : set_error((int)e, "qp_former_backward_kernel launch");
 }
-
-size_t srbd_mpc_backward_workspace_doubles(int horizon, int batch) {
-  return 2 * srbd_mpc_workspace_doubles(horizon, batch);  // the QP and its six gradients
-}
-
-int srbd_mpc_backward(int horizon, int batch, const double* const* former_inputs, const double* const* iterate,
-                      const double* grad_x, double* workspace, double* const* input_grads, int* status,
-                      void* stream) {
-  if (!horizon_ok(horizon) || batch < 0 || !former_inputs || !iterate || !input_grads)
-    return set_error(kErrInvalid, "srbd_mpc_backward: bad arguments");
-  if (batch == 0) return 0;
-  if (!workspace || !grad_x || !iterate[0] || !iterate[1] || !iterate[2] || !iterate[3])
-    return set_error(kErrInvalid, "srbd_mpc_backward: null workspace / grad_x / iterate");
-  const size_t N = (size_t)horizon, B = (size_t)batch;
-  const size_t w[6] = {24 * N, 24 * N, 122 * N - 24, 14 * N, 28 * N, 16 * N};  // H, f, A, b, G, d
-  double* qp[6];
-  double* gr[6];
-  double* o = workspace;
-  for (int i = 0; i < 12; ++i) {
-    (i < 6 ? qp[i] : gr[i - 6]) = o;
-    o += B * w[i % 6];
-  }
-  if (int rc = srbd_qp_former(horizon, batch, former_inputs, qp, stream)) return rc;
-  const double* sin[10] = {qp[0], qp[4], qp[2], qp[1], qp[5], qp[3], iterate[0], iterate[1], iterate[2], iterate[3]};
-  if (int rc = srbd_pdipm_backward(horizon, batch, sin, grad_x, gr, status, stream)) return rc;
-  return srbd_qp_former_backward(horizon, batch, former_inputs, gr, input_grads, stream);
-}
-
-// ---- several seeds at one iterate (pdipm_backward.hpp: one factorisation, M solves) ----
-
-namespace {
-
-// batch * n_seeds gradient rows must fit the launch grid's int
-bool seed_rows_ok(int batch, int n_seeds) { return (long long)batch * (long long)n_seeds <= (long long)INT_MAX; }
 
 // the QP gradients (bit o: H, f, A, b, G, d) the gradient of former input i reads: the table in the
 // header comment of qp_former_backward.hpp
@@ -823,11 +821,11 @@ constexpr unsigned kFormerGradDeps[17] = {
     kGradA | kGradB,  // residual angular acceleration
 };
 
-// the union of the dependencies of the inputs in input_mask (bit i = former input i; 0 = all 17)
+// the union of the dependencies of the inputs in input_mask (bit i = former input i)
 unsigned qp_grads_needed(unsigned input_mask) {
   unsigned need = 0;
   for (int i = 0; i < 17; ++i)
-    if (input_mask == 0 || (input_mask >> i & 1u)) need |= kFormerGradDeps[i];
+    if (input_mask >> i & 1u) need |= kFormerGradDeps[i];
   return need;
 }
 
@@ -840,90 +838,22 @@ void qp_widths(int horizon, size_t (&w)[6]) {  // H, f, A, b, G, d
   w[5] = 16 * N;
 }
 
-}  // namespace
-
-int srbd_pdipm_backward_multi(int horizon, int batch, int n_seeds, const double* const* inputs,
-                              const double* grad_x, size_t grad_x_env_stride, double* const* qp_grads,
-                              int* status, void* stream) {
-  if (!horizon_ok(horizon) || batch < 0 || n_seeds < 1 || !inputs || !qp_grads)
-    return set_error(kErrInvalid, "srbd_pdipm_backward_multi: bad arguments");
-  if (grad_x_env_stride != 0 && grad_x_env_stride != (size_t)n_seeds * 24 * (size_t)horizon)
-    return set_error(kErrInvalid, "srbd_pdipm_backward_multi: grad_x_env_stride must be 0 or n_seeds * 24 * horizon");
-  if (!seed_rows_ok(batch, n_seeds))
-    return set_error(kErrInvalid, "srbd_pdipm_backward_multi: batch * n_seeds overflows");
-  if (batch == 0) return 0;
-  srbd::BackwardMultiArgs a{};
-  for (int i = 0; i < 10; ++i) {
-    if (!inputs[i] && !(i >= 3 && i <= 5)) return set_error(kErrInvalid, "srbd_pdipm_backward_multi: null input");
-    a.in[i] = inputs[i];  // f, h, b (3..5) are not read
-  }
-  if (!grad_x) return set_error(kErrInvalid, "srbd_pdipm_backward_multi: null grad_x");
-  a.grad_x = grad_x;
-  a.env_stride = grad_x_env_stride;
-  for (int i = 0; i < 6; ++i) a.out[i] = qp_grads[i];  // null: not written
-  a.status = status;
-  a.N = horizon;
-  a.batch = batch;
-  a.n_seeds = n_seeds;
-  static srbd::LdsAttr cfg_backward_multi;
-  const size_t lds = srbd::backward_lds_bytes(horizon);
-  if (lds > 160 * 1024) return set_error(kErrInvalid, "horizon too large for the LDS-resident backward solve");
-  if (int rc = ensure_lds_attr(srbd::bwd::adjoint_multi_kernel(), lds, cfg_backward_multi)) return rc;
-  srbd::bwd::launch_adjoint_multi(a, lds, (hipStream_t)stream);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : set_error((int)e, "pdipm_backward_multi_kernel launch");
-}
-
-int srbd_qp_former_backward_multi(int horizon, int batch, int n_seeds, const double* const* former_inputs,
-                                  const double* const* qp_grads, double* const* input_grads, void* stream) {
-  if (!horizon_ok(horizon) || batch < 0 || n_seeds < 1 || !former_inputs || !qp_grads || !input_grads)
-    return set_error(kErrInvalid, "srbd_qp_former_backward_multi: bad arguments");
-  if (!seed_rows_ok(batch, n_seeds))
-    return set_error(kErrInvalid, "srbd_qp_former_backward_multi: batch * n_seeds overflows");
-  if (batch == 0) return 0;
-  srbd::FormerBackwardArgs a{};
-  for (int i = 0; i < 17; ++i) {
-    if (!former_inputs[i]) return set_error(kErrInvalid, "srbd_qp_former_backward_multi: null input");
-    a.in[i] = former_inputs[i];
-    a.out[i] = input_grads[i];  // null: not written
-  }
-  for (int i = 0; i < 6; ++i) a.g[i] = qp_grads[i];  // null: a zero gradient
-  a.N = horizon;
-  a.batch = batch;
-  a.n_seeds = n_seeds;
-  srbd::bwd::launch_former_backward(a, (hipStream_t)stream);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : set_error((int)e, "qp_former_backward_kernel launch");
-}
-
-unsigned srbd_former_grad_deps(int input) { return input >= 0 && input < 17 ? kFormerGradDeps[input] : 0u; }
-
-size_t srbd_mpc_backward_multi_workspace_doubles(int horizon, int batch, int n_seeds, unsigned input_mask) {
-  if (!horizon_ok(horizon) || batch < 0 || n_seeds < 1 || !seed_rows_ok(batch, n_seeds)) return 0;
-  size_t w[6];
-  qp_widths(horizon, w);
-  const unsigned need = qp_grads_needed(input_mask);
-  size_t per_env = 0;
-  for (int o = 0; o < 6; ++o) per_env += w[o] + ((need >> o & 1u) ? (size_t)n_seeds * w[o] : 0);
-  return (size_t)batch * per_env;  // the QP, then the needed gradients, (B, M, width) each
-}
-
-int srbd_mpc_backward_multi(int horizon, int batch, int n_seeds, const double* const* former_inputs,
-                            const double* const* iterate, const double* grad_x, size_t grad_x_env_stride,
-                            double* workspace, double* const* input_grads, int* status, void* stream) {
-  if (!horizon_ok(horizon) || batch < 0 || n_seeds < 1 || !former_inputs || !iterate || !input_grads)
-    return set_error(kErrInvalid, "srbd_mpc_backward_multi: bad arguments");
-  if (grad_x_env_stride != 0 && grad_x_env_stride != (size_t)n_seeds * 24 * (size_t)horizon)
-    return set_error(kErrInvalid, "srbd_mpc_backward_multi: grad_x_env_stride must be 0 or n_seeds * 24 * horizon");
-  if (!seed_rows_ok(batch, n_seeds))
-    return set_error(kErrInvalid, "srbd_mpc_backward_multi: batch * n_seeds overflows");
+// former -> adjoint -> former VJP. The workspace holds the QP, then the QP gradients the non-null
+// input_grads read, (B, M, width) each; the others are null to both kernels (the adjoint kernel skips a
+// null output, the VJP reads a null gradient as zero). Whether asking for no gradient at all is an error
+// (`need_request`) is the calling entry's business.
+int mpc_backward_impl(const char* what, bool need_request, int horizon, int batch, int n_seeds,
+                      const double* const* former_inputs, const double* const* iterate, const double* grad_x,
+                      size_t env_stride, double* workspace, double* const* input_grads, int* status, void* stream) {
+  if (int rc = check_seeds(what, horizon, batch, n_seeds, env_stride, former_inputs && iterate && input_grads))
+    return rc;
   if (batch == 0) return 0;
   if (!workspace || !grad_x || !iterate[0] || !iterate[1] || !iterate[2] || !iterate[3])
-    return set_error(kErrInvalid, "srbd_mpc_backward_multi: null workspace / grad_x / iterate");
+    return fail(what, "null workspace / grad_x / iterate");
   unsigned input_mask = 0;
   for (int i = 0; i < 17; ++i)
     if (input_grads[i]) input_mask |= 1u << i;
-  if (input_mask == 0) return set_error(kErrInvalid, "srbd_mpc_backward_multi: no input gradient requested");
+  if (need_request && input_mask == 0) return fail(what, "no input gradient requested");
   const unsigned need = qp_grads_needed(input_mask);
   const size_t B = (size_t)batch, M = (size_t)n_seeds;
   size_t w[6];
@@ -935,15 +865,70 @@ int srbd_mpc_backward_multi(int horizon, int batch, int n_seeds, const double* c
     qp[i] = o;
     o += B * w[i];
   }
-  for (int i = 0; i < 6; ++i) {  // only the gradients the requested inputs read; the others stay NULL
+  for (int i = 0; i < 6; ++i) {
     gr[i] = (need >> i & 1u) ? o : nullptr;
     if (gr[i]) o += B * M * w[i];
   }
   if (int rc = srbd_qp_former(horizon, batch, former_inputs, qp, stream)) return rc;
   const double* sin[10] = {qp[0], qp[4], qp[2], qp[1], qp[5], qp[3], iterate[0], iterate[1], iterate[2], iterate[3]};
-  if (int rc = srbd_pdipm_backward_multi(horizon, batch, n_seeds, sin, grad_x, grad_x_env_stride, gr, status, stream))
-    return rc;
-  return srbd_qp_former_backward_multi(horizon, batch, n_seeds, former_inputs, gr, input_grads, stream);
+  if (int rc = adjoint_impl(what, horizon, batch, n_seeds, sin, grad_x, env_stride, gr, status, stream)) return rc;
+  return former_vjp_impl(what, horizon, batch, n_seeds, former_inputs, gr, input_grads, stream);
+}
+
+}  // namespace
+
+int srbd_pdipm_backward(int horizon, int batch, const double* const* inputs, const double* grad_x,
+                        double* const* qp_grads, int* status, void* stream) {
+  return adjoint_impl("srbd_pdipm_backward", horizon, batch, 1, inputs, grad_x, 24 * (size_t)horizon, qp_grads,
+                      status, stream);
+}
+
+int srbd_pdipm_backward_multi(int horizon, int batch, int n_seeds, const double* const* inputs,
+                              const double* grad_x, size_t grad_x_env_stride, double* const* qp_grads,
+                              int* status, void* stream) {
+  return adjoint_impl("srbd_pdipm_backward_multi", horizon, batch, n_seeds, inputs, grad_x, grad_x_env_stride,
+                      qp_grads, status, stream);
+}
+
+int srbd_qp_former_backward(int horizon, int batch, const double* const* former_inputs,
+                            const double* const* qp_grads, double* const* input_grads, void* stream) {
+  return former_vjp_impl("srbd_qp_former_backward", horizon, batch, 1, former_inputs, qp_grads, input_grads, stream);
+}
+
+int srbd_qp_former_backward_multi(int horizon, int batch, int n_seeds, const double* const* former_inputs,
+                                  const double* const* qp_grads, double* const* input_grads, void* stream) {
+  return former_vjp_impl("srbd_qp_former_backward_multi", horizon, batch, n_seeds, former_inputs, qp_grads,
+                         input_grads, stream);
+}
+
+unsigned srbd_former_grad_deps(int input) { return input >= 0 && input < 17 ? kFormerGradDeps[input] : 0u; }
+
+size_t srbd_mpc_backward_multi_workspace_doubles(int horizon, int batch, int n_seeds, unsigned input_mask) {
+  if (!horizon_ok(horizon) || batch < 0 || n_seeds < 1 || !seed_rows_ok(batch, n_seeds)) return 0;
+  size_t w[6];
+  qp_widths(horizon, w);
+  const unsigned need = qp_grads_needed(input_mask ? input_mask : ~0u);  // 0 = all 17
+  size_t per_env = 0;
+  for (int o = 0; o < 6; ++o) per_env += w[o] + ((need >> o & 1u) ? (size_t)n_seeds * w[o] : 0);
+  return (size_t)batch * per_env;  // what mpc_backward_impl carves
+}
+
+size_t srbd_mpc_backward_workspace_doubles(int horizon, int batch) {
+  return 2 * srbd_mpc_workspace_doubles(horizon, batch);  // the QP and all six gradients: an upper bound
+}
+
+int srbd_mpc_backward(int horizon, int batch, const double* const* former_inputs, const double* const* iterate,
+                      const double* grad_x, double* workspace, double* const* input_grads, int* status,
+                      void* stream) {  // all 17 input_grads may be null: only `status` is written then
+  return mpc_backward_impl("srbd_mpc_backward", false, horizon, batch, 1, former_inputs, iterate, grad_x,
+                           24 * (size_t)horizon, workspace, input_grads, status, stream);
+}
+
+int srbd_mpc_backward_multi(int horizon, int batch, int n_seeds, const double* const* former_inputs,
+                            const double* const* iterate, const double* grad_x, size_t grad_x_env_stride,
+                            double* workspace, double* const* input_grads, int* status, void* stream) {
+  return mpc_backward_impl("srbd_mpc_backward_multi", true, horizon, batch, n_seeds, former_inputs, iterate, grad_x,
+                           grad_x_env_stride, workspace, input_grads, status, stream);
 }
 
 int srbd_pattern_ccs(int horizon, int which, int* colptr, int* rowind) {

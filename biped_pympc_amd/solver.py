@@ -233,16 +233,32 @@ def mpc_solve(former_inputs: list[torch.Tensor], N: int, n_iter: int, y0: float 
 
 # ---- backward pass: gradients of a loss L(x) through the QP solve and the former ----
 
-def _optional_outputs(outputs, widths, B: int, device, what: str):
-    """None -> every output allocated; a list -> its tensors, None entries stay unwritten (NULL)."""
+def _optional_outputs(outputs, widths, B: int, device, what: str, M: int | None = None, want=None):
+    """(B, width) outputs, or (B, M, width) for M seeds: None -> those in `want` (default all)
+    allocated; a list -> its tensors, None entries stay unwritten (NULL)."""
     if outputs is None:
-        outputs = [torch.empty((B, w), dtype=torch.float64, device=device) for w in widths]
-    _check_batch(outputs, widths, B, what)
+        outputs = [torch.empty((B, w) if M is None else (B, M, w), dtype=torch.float64, device=device)
+                   if want is None or i in want else None for i, w in enumerate(widths)]
+    _check_batch(outputs, [(M or 1) * w for w in widths], B, what)
     return list(outputs)
 
 
 def _ptrs(tensors):
     return _native.ptr_array([t.data_ptr() if t is not None else 0 for t in tensors])
+
+
+def _require_qp_and_iterate(ins, what: str) -> None:
+    if any(ins[i] is None for i in (0, 1, 2, 6, 7, 8, 9)):
+        raise ValueError(f"{what}: Q_val, G_val, A_val and the iterate x, s, z, y are required")
+
+
+def _workspace(workspace, n: int, device, what: str) -> torch.Tensor:
+    """The caller's workspace checked against the `n` doubles the C entry asks for, or a new one."""
+    if workspace is None:
+        workspace = torch.empty(max(n, 1), dtype=torch.float64, device=device)
+    if not workspace.is_cuda or workspace.dtype != torch.float64 or workspace.numel() < n or not workspace.is_contiguous():
+        raise ValueError(f"{what}: workspace must be a contiguous CUDA float64 tensor of >= {n} elements")
+    return workspace
 
 
 def pdipm_backward(qp: list, iterate: list[torch.Tensor], grad_x: torch.Tensor, N: int,
@@ -259,8 +275,7 @@ def pdipm_backward(qp: list, iterate: list[torch.Tensor], grad_x: torch.Tensor, 
     B = grad_x.shape[0]
     ins = list(qp) + list(iterate)
     _check_batch(ins + [grad_x], d.solver_in_nnz + (d.nz,), B, "pdipm_backward")
-    if any(ins[i] is None for i in (0, 1, 2, 6, 7, 8, 9)):
-        raise ValueError("pdipm_backward: Q_val, G_val, A_val and the iterate x, s, z, y are required")
+    _require_qp_and_iterate(ins, "pdipm_backward")
     outs = _optional_outputs(outputs, d.former_out_nnz, B, grad_x.device, "pdipm_backward outputs")
     st = _check_status(status, B, "pdipm_backward")
     rc = _native.lib().srbd_pdipm_backward(N, B, _ptrs(ins), grad_x.data_ptr(), _ptrs(outs), st, _stream_ptr())
@@ -297,11 +312,7 @@ def mpc_backward(former_inputs: list[torch.Tensor], iterate: list[torch.Tensor],
     _check_batch(list(iterate) + [grad_x], d.solver_in_nnz[6:] + (d.nz,), B, "mpc_backward iterate")
     outs = _optional_outputs(outputs, d.former_in_nnz, B, grad_x.device, "mpc_backward outputs")
     L = _native.lib()
-    n = L.srbd_mpc_backward_workspace_doubles(N, B)
-    if workspace is None:
-        workspace = torch.empty(max(n, 1), dtype=torch.float64, device=grad_x.device)
-    if not workspace.is_cuda or workspace.dtype != torch.float64 or workspace.numel() < n or not workspace.is_contiguous():
-        raise ValueError(f"mpc_backward: workspace must be a contiguous CUDA float64 tensor of >= {n} elements")
+    workspace = _workspace(workspace, L.srbd_mpc_backward_workspace_doubles(N, B), grad_x.device, "mpc_backward")
     st = _check_status(status, B, "mpc_backward")
     rc = L.srbd_mpc_backward(N, B, _ptrs(former_inputs), _ptrs(iterate), grad_x.data_ptr(), workspace.data_ptr(),
                              _ptrs(outs), st, _stream_ptr())
@@ -332,16 +343,6 @@ def _seed_block(grad_x: torch.Tensor, B: int, N: int, what: str):
                      f"got {tuple(grad_x.shape)}")
 
 
-def _seed_outputs(outputs, widths, B: int, M: int, device, what: str, want=None):
-    """(B, M, width) outputs: None -> those in `want` (default all) allocated; a list -> its tensors,
-    None entries stay unwritten (NULL)."""
-    if outputs is None:
-        outputs = [torch.empty((B, M, w), dtype=torch.float64, device=device) if want is None or i in want else None
-                   for i, w in enumerate(widths)]
-    _check_batch(outputs, [M * w for w in widths], B, what)
-    return list(outputs)
-
-
 def pdipm_backward_multi(qp: list, iterate: list[torch.Tensor], grad_x: torch.Tensor, N: int,
                          status: torch.Tensor | None = None, outputs: list | None = None):
     """``pdipm_backward`` for M seeds at one iterate with one factorisation and M solves.
@@ -357,10 +358,9 @@ def pdipm_backward_multi(qp: list, iterate: list[torch.Tensor], grad_x: torch.Te
     B = iterate[0].shape[0]
     ins = list(qp) + list(iterate)
     _check_batch(ins, d.solver_in_nnz, B, "pdipm_backward_multi")
-    if any(ins[i] is None for i in (0, 1, 2, 6, 7, 8, 9)):
-        raise ValueError("pdipm_backward_multi: Q_val, G_val, A_val and the iterate x, s, z, y are required")
+    _require_qp_and_iterate(ins, "pdipm_backward_multi")
     M, stride = _seed_block(grad_x, B, N, "pdipm_backward_multi")
-    outs = _seed_outputs(outputs, d.former_out_nnz, B, M, grad_x.device, "pdipm_backward_multi outputs")
+    outs = _optional_outputs(outputs, d.former_out_nnz, B, grad_x.device, "pdipm_backward_multi outputs", M)
     st = _check_status(status, B, "pdipm_backward_multi")
     rc = _native.lib().srbd_pdipm_backward_multi(N, B, M, _ptrs(ins), grad_x.data_ptr(), stride, _ptrs(outs), st,
                                                  _stream_ptr())
@@ -384,7 +384,8 @@ def qp_former_backward_multi(former_inputs: list[torch.Tensor], qp_grads: list, 
         raise ValueError(f"qp_former_backward_multi: gradients must be ({B}, M, width), got {tuple(g0.shape)}")
     M = g0.shape[1]
     _check_batch(qp_grads, [M * w for w in d.former_out_nnz], B, "qp_former_backward_multi gradients")
-    outs = _seed_outputs(outputs, d.former_in_nnz, B, M, former_inputs[0].device, "qp_former_backward_multi outputs")
+    outs = _optional_outputs(outputs, d.former_in_nnz, B, former_inputs[0].device, "qp_former_backward_multi outputs",
+                             M)
     rc = _native.lib().srbd_qp_former_backward_multi(N, B, M, _ptrs(former_inputs), _ptrs(qp_grads), _ptrs(outs),
                                                      _stream_ptr())
     _native.check(rc, "srbd_qp_former_backward_multi")
@@ -423,13 +424,10 @@ def mpc_backward_multi(former_inputs: list[torch.Tensor], iterate: list[torch.Te
     mask = _input_mask(want)
     if mask == 0:
         raise ValueError("mpc_backward_multi: no former input requested")
-    outs = _seed_outputs(outputs, d.former_in_nnz, B, M, grad_x.device, "mpc_backward_multi outputs", want)
+    outs = _optional_outputs(outputs, d.former_in_nnz, B, grad_x.device, "mpc_backward_multi outputs", M, want)
     L = _native.lib()
-    n = L.srbd_mpc_backward_multi_workspace_doubles(N, B, M, mask)
-    if workspace is None:
-        workspace = torch.empty(max(n, 1), dtype=torch.float64, device=grad_x.device)
-    if not workspace.is_cuda or workspace.dtype != torch.float64 or workspace.numel() < n or not workspace.is_contiguous():
-        raise ValueError(f"mpc_backward_multi: workspace must be a contiguous CUDA float64 tensor of >= {n} elements")
+    workspace = _workspace(workspace, L.srbd_mpc_backward_multi_workspace_doubles(N, B, M, mask), grad_x.device,
+                           "mpc_backward_multi")
     st = _check_status(status, B, "mpc_backward_multi")
     rc = L.srbd_mpc_backward_multi(N, B, M, _ptrs(former_inputs), _ptrs(iterate), grad_x.data_ptr(), stride,
                                    workspace.data_ptr(), _ptrs(outs), st, _stream_ptr())

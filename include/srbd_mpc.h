@@ -356,8 +356,11 @@ int srbd_qp_former_backward(int horizon, int batch, const double* const* former_
                             const double* const* qp_grads, double* const* input_grads, void* stream);
 
 /* srbd_qp_former -> srbd_pdipm_backward -> srbd_qp_former_backward in one call (same bits): the QP and
- * its six gradients go to `workspace`, caller-owned device memory of
- * srbd_mpc_backward_workspace_doubles(horizon, batch) doubles. iterate: x, s, z, y of the solve. */
+ * its gradients go to `workspace`, caller-owned device memory of
+ * srbd_mpc_backward_workspace_doubles(horizon, batch) doubles. That size (the QP and all six gradients)
+ * is an upper bound: only the gradients that the non-NULL input_grads read are materialised, as in
+ * srbd_mpc_backward_multi. All 17 input_grads may be NULL here: only `status` is written then.
+ * iterate: x, s, z, y of the solve. */
 size_t srbd_mpc_backward_workspace_doubles(int horizon, int batch);
 int srbd_mpc_backward(int horizon, int batch, const double* const* former_inputs,
                       const double* const* iterate /* x, s, z, y */, const double* grad_x,
@@ -366,8 +369,8 @@ int srbd_mpc_backward(int horizon, int batch, const double* const* former_inputs
 /* ---- Several seeds at one iterate: solution Jacobians and the u0 feedback gain ----------------------
  * K depends on the QP and the iterate only, so n_seeds = M seeds g_0 .. g_{M-1} on x share the load, the
  * stage-invariance check and the factorisation: one factorisation and M solves (each with its refinement
- * step) in one launch. Seed k's results have the bits srbd_pdipm_backward returns for g_k alone. The
- * result is, as there, the derivative of the linearised KKT conditions at the iterate: exact at
+ * step) in one launch. n_seeds = 1 is srbd_pdipm_backward, and seed k's results have the bits of a call
+ * with g_k alone. The result is, as there, the derivative of the linearised KKT conditions at the iterate: exact at
  * convergence. Conventions as the entry points above (host arrays of device pointers, asynchronous, no
  * device allocation, batch == 0 returns 0 and bad arguments an error code without touching the GPU).
  * Bad arguments: horizon outside 1..32, n_seeds < 1, a stride that is neither 0 nor n_seeds * 24N, a

@@ -46,4 +46,7 @@ def test_backward_workspace_is_the_qp_and_its_gradients():
     assert L.srbd_mpc_backward_workspace_doubles(10, 4096) == 2 * L.srbd_mpc_workspace_doubles(10, 4096)
     assert L.srbd_mpc_backward_workspace_doubles(10, 4096) == 2 * 4096 * 2256
     assert L.srbd_mpc_backward_workspace_doubles(0, 4) == 0 and L.srbd_mpc_backward_workspace_doubles(33, 4) == 0
+    for N in (1, 2, 10, 32):  # an upper bound of what the one-seed composition carves for any request
+        for B in (1, 16, 4096):
+            assert L.srbd_mpc_backward_multi_workspace_doubles(N, B, 1, 0) <= L.srbd_mpc_backward_workspace_doubles(N, B)
     assert _native.STATUS_UNSUPPORTED == 8

@@ -247,3 +247,38 @@ def test_mpc_backward_replays_from_a_hip_graph():
     torch.cuda.synchronize()
     for i in range(17):
         assert torch.equal(out[i], eager[i]), layout.FORMER_IN_NAMES[i]
+
+
+# ---- 9. the composition's single-seed entry: no output requested, and its workspace bound -----------
+
+def test_mpc_backward_with_every_output_null_writes_the_status_only():
+    """srbd_mpc_backward accepts 17 null input_grads (srbd_mpc_backward_multi rejects them): it runs the
+    chain and the status words are those of the adjoint solve."""
+    N, K = 3, 5
+    ins = _cuda(C.workload(N, "random")[0])
+    it = _cuda(C.iterate(N, "random", K))
+    g = _cuda(C.seeds(N))[0]
+    st = torch.full((C.BATCH,), -1, dtype=torch.int32, device="cuda")
+    outs = solver.mpc_backward(ins, it, g, N, status=st, outputs=[None] * 17)
+    torch.cuda.synchronize()
+    assert outs == [None] * 17
+    assert torch.all(st == 0), st
+
+
+def test_mpc_backward_stays_inside_the_documented_workspace():
+    """All 17 outputs (so all six QP gradients) with a workspace of exactly
+    srbd_mpc_backward_workspace_doubles(N, B) doubles: the 1024 doubles behind it keep their sentinel."""
+    N, K, guard = 2, 5, 1024
+    ins = _cuda(C.workload(N, "random")[0])
+    it = _cuda(C.iterate(N, "random", K))
+    g = _cuda(C.seeds(N))[0]
+    n = _native.lib().srbd_mpc_backward_workspace_doubles(N, C.BATCH)
+    sentinel = -0x5A5A5A5A5A5A5A5B
+    buf = torch.full((n + guard,), sentinel, dtype=torch.int64, device="cuda").view(torch.float64)
+    st = torch.full((C.BATCH,), -1, dtype=torch.int32, device="cuda")
+    outs = solver.mpc_backward(ins, it, g, N, status=st, workspace=buf[:n])
+    torch.cuda.synchronize()
+    assert torch.all(st == 0), st
+    assert all(o is not None and torch.isfinite(o).all() for o in outs)
+    assert torch.all(buf[n:].view(torch.int64) == sentinel)
+    assert not torch.all(buf[:n].view(torch.int64) == sentinel)  # the workspace itself was used
