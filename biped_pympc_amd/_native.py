@@ -145,8 +145,35 @@ def lib() -> ctypes.CDLL:
     L.srbd_mpc_backward_multi.restype = ctypes.c_int
     L.srbd_mpc_backward_multi.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, P, P, _c_dp, ctypes.c_size_t,
                                           _c_dp, P, _c_dp, ctypes.c_void_p]
+    # the backward pass of the controller step's FP32 ends: wrench / torque VJP, input-preparation VJP, the chain
+    L.srbd_u0_wrench_backward.restype = ctypes.c_int
+    L.srbd_u0_wrench_backward.argtypes = [ctypes.c_int, ctypes.c_int, _c_dp, _c_dp, _c_dp, ctypes.c_int, _c_dp, _c_dp,
+                                          _c_dp, _c_dp, _c_dp, ctypes.c_void_p]
+    L.srbd_prepare_inputs_backward.restype = ctypes.c_int
+    L.srbd_prepare_inputs_backward.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(MPCPrep), P, _c_dp, _c_dp,
+                                               _c_dp, P, ctypes.c_void_p]
+    L.srbd_prep_grad_deps.restype = ctypes.c_uint
+    L.srbd_prep_grad_deps.argtypes = [ctypes.c_int]
+    L.srbd_mpc_step_backward_workspace_doubles.restype = ctypes.c_size_t
+    L.srbd_mpc_step_backward_workspace_doubles.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint]
+    L.srbd_mpc_step_backward.restype = ctypes.c_int
+    L.srbd_mpc_step_backward.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(MPCPrep), P, P, _c_dp, ctypes.c_int,
+                                         _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, P, _c_dp, ctypes.c_void_p]
     _lib = L
     return L
+
+
+# the 15 gradients of srbd_prepare_inputs_backward in SRBD_PREP_GRAD_* order (include/srbd_mpc.h): the
+# field of srbd_mpc_prep each belongs to, and its per-env shape at horizon N
+PREP_GRAD_NAMES = ("root_euler", "root_position", "root_angular_velocity_w", "root_velocity_w", "rotation_body",
+                   "foot_position", "desired_velocity_b", "desired_angular_velocity_b", "desired_height",
+                   "world_position_desired", "yaw_desired", "contact_table", "dt_mpc", "residual_lin_accel",
+                   "residual_ang_accel")
+
+
+def prep_grad_shape(name: str, N: int) -> tuple:
+    return {"rotation_body": (3, 3), "foot_position": (2, 3), "desired_height": (), "yaw_desired": (),
+            "contact_table": (N, 2), "dt_mpc": ()}.get(name, (3,))
 
 
 class _Tolerant:

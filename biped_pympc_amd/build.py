@@ -86,11 +86,11 @@ def source_hash(sources: list[str] | None = None) -> str:
 
 def _unit_hash(unit: str, cmd: list[str], sources: list[str]) -> str:
     """What one object file depends on: its flags (for the main unit they carry the library's build
-    id, which it embeds), its source and every header (csrc/*.hpp; include/srbd_mpc.h for the main
-    unit, the only one that includes it)."""
+    id, which it embeds), its source and every header (csrc/*.hpp; include/srbd_mpc.h for the main and
+    the backward unit, the two that include it)."""
     parts = [unit, repr(cmd[1:cmd.index("-o")])]
     for s in [cmd[-1]] + [h for h in sources if not h.endswith(".hip")]:
-        if s.endswith(".h") and unit != "srbd_mpc.hip":
+        if s.endswith(".h") and unit not in ("srbd_mpc.hip", "srbd_backward.hip"):
             continue
         parts += [os.path.basename(s), open(s, "rb").read()]
     return _digest(parts)
@@ -135,7 +135,7 @@ HIP_UNITS = {
     "srbd_mpc.hip": ["-DSRBD_SPLIT_REG20"],
     "srbd_reg20.hip": ["-mllvm", "-amdgpu-use-amdgpu-trackers=1"],
     "srbd_regN.hip": ["-mllvm", "-amdgpu-use-amdgpu-trackers=1"],  # the other register horizons
-    "srbd_backward.hip": [],  # the backward pass: adjoint KKT solve, QP-data gradients, former VJP
+    "srbd_backward.hip": [],  # the backward pass: adjoint KKT solve, QP-data gradients, former / prep / wrench VJPs
 }
 
 

@@ -59,6 +59,8 @@ class MPCConf:
     #                              and the 17 prepared former inputs to .former_inputs
     compute_cost: bool = False   # fill run()'s cost with the QP objective 0.5 x^T H x + f^T x of the solution
     #                              (the reference's MPCController.mpc_cost; its CusADi back end returns zeros)
+    differentiable: bool = False  # keep what backward() / run_autograd() need of a step (with keep_solution):
+    #                               the step then snapshots first_run before its launch; nothing else changes
 
 
 @dataclass
@@ -194,12 +196,18 @@ class MPCControllerHIP(BaseMPCController):
         # solution, 2 step length at its floor in the last iteration): set to an int32 (B,) tensor
         # on the device to have run() fill it (None: not computed)
         self.status = None
+        # cfg.differentiable: first_run as it was before the last step (the step clears it), and the
+        # float32 tensors that step read (backward() reads them again)
+        self._first_run_prev = torch.empty(B, dtype=torch.bool, device=dev)
+        self._step_tensors = None
+        self._step_record = None
         return self
 
-    def _prep_struct(self, keep: list, strict: bool = False) -> _native.MPCPrep:
+    def _prep_struct(self, keep: list, strict: bool = False, overrides: dict | None = None) -> _native.MPCPrep:
         """The device-pointer struct of one step. strict (graph capture): every tensor must already
         be float32, contiguous and on the controller's device -- a converted copy would be baked
-        into the graph and never see the caller's in-place updates."""
+        into the graph and never see the caller's in-place updates. overrides (run_autograd): tensors
+        that stand in for the controller's own, by field name, for this struct only."""
         st, ds, dev = self.state_estimate_data, self.desired_state_data, self.device
         if st is None or ds is None:
             raise RuntimeError("set_state_estimate_data / set_desired_state_data before run()")
@@ -215,12 +223,19 @@ class MPCControllerHIP(BaseMPCController):
             keep.append(t)
             return t.data_ptr()
 
+        used = {}
+
+        def src(obj, name):  # the float32 tensor this step reads for `name`
+            t = overrides[name] if overrides and name in overrides else getattr(obj, name)
+            used[name] = f32(t, name)
+            return used[name]
+
         p = _native.MPCPrep()
         for name in ("root_euler", "root_position", "root_angular_velocity_w", "root_velocity_w",
                      "rotation_body", "foot_position"):
-            setattr(p, name, ptr(f32(getattr(st, name), name)))
+            setattr(p, name, ptr(src(st, name)))
         for name in ("desired_velocity_b", "desired_angular_velocity_b", "desired_height"):
-            setattr(p, name, ptr(f32(getattr(ds, name), name)))
+            setattr(p, name, ptr(src(ds, name)))
         for name in ("world_position_desired", "yaw_desired"):  # updated in place by the kernel
             t = getattr(self, name)
             if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
@@ -233,10 +248,10 @@ class MPCControllerHIP(BaseMPCController):
         if self._gait is not None:
             p.gait_phase, p.ssp_durations, p.dsp_durations = (ptr(t) for t in self._gait)
         else:
-            p.contact_table = ptr(f32(self.contact_table, "contact_table"))
-        p.dt_mpc = ptr(f32(self.dt_mpc, "dt_mpc"))
-        p.residual_lin_accel = ptr(f32(self.residual_lin_accel, "residual_lin_accel"))
-        p.residual_ang_accel = ptr(f32(self.residual_ang_accel, "residual_ang_accel"))
+            p.contact_table = ptr(src(self, "contact_table"))
+        p.dt_mpc = ptr(src(self, "dt_mpc"))
+        p.residual_lin_accel = ptr(src(self, "residual_lin_accel"))
+        p.residual_ang_accel = ptr(src(self, "residual_ang_accel"))
         p.I_body[:] = [float(v) for v in self.I_body.reshape(-1).tolist()]
         p.mass, p.mu = float(self.mass), float(self.mu)
         q = [float(v) for v in torch.as_tensor(self.Q, dtype=torch.float32).reshape(-1).tolist()]
@@ -248,6 +263,8 @@ class MPCControllerHIP(BaseMPCController):
         # torch evaluates `decimation * dt * tensor` with the Python product cast to float32
         p.step_dt = float(torch.tensor(self.cfg.decimation * self.cfg.dt, dtype=torch.float32))
         p.literal_layout = 1 if self.cfg.literal_layout else 0
+        if self.cfg.differentiable:
+            self._step_tensors = used
         return p
 
     def prepare(self) -> list[torch.Tensor]:
@@ -271,6 +288,8 @@ class MPCControllerHIP(BaseMPCController):
                 self.foot_wrench.data_ptr(), 0 if J is None else J.shape[3], None if J is None else J.data_ptr(),
                 None if cb is None else cb.data_ptr(), None if J is None else self.tau.data_ptr())
         st = solver._check_status(self.status, B, "MPCControllerHIP.status")
+        if self.cfg.differentiable:  # the step clears first_run; its backward pass needs the flag it read
+            self._first_run_prev.copy_(self.first_run)
         if self.cfg.compute_cost:
             rc = _native.lib().srbd_mpc_step_info(*args, _native.solve_info(st, None, self._cost_ptr()),
                                                   solver._stream_ptr())
@@ -280,6 +299,10 @@ class MPCControllerHIP(BaseMPCController):
             rc = _native.lib().srbd_mpc_step(*args, solver._stream_ptr())
         _native.check(rc, "srbd_mpc_step")
         self.solution = self.buffers.outputs if self.cfg.keep_solution else None
+        self._step_record = None
+        if self.cfg.differentiable and self.cfg.keep_solution and self._step_tensors is not None:
+            self._step_record = _StepRecord(p, self._step_tensors, self._first_run_prev, self.former_inputs,
+                                            list(self.solution[:4]), N, B)
 
     def _cost_ptr(self) -> int:
         return solver._check_objective(self.cost, self.num_envs, "MPCControllerHIP.cost", torch.float32, "cost")
@@ -303,11 +326,66 @@ class MPCControllerHIP(BaseMPCController):
                                "solution the gain is linearised at")
         return solver.mpc_feedback_gain(self.former_inputs, list(self.solution[:4]), self.horizon_length)
 
+    # ---- backward pass of the step: wrench cotangent -> the controller's own float32 tensors ----
+
+    def _require_record(self, what: str) -> "_StepRecord":
+        if not (self.cfg.keep_solution and self.cfg.differentiable) or self._step_record is None:
+            raise RuntimeError(f"MPCControllerHIP.{what}() needs cfg.keep_solution=True and cfg.differentiable=True "
+                               "and a step run with both: without them the step keeps neither the former inputs "
+                               "and the solution it is linearised at nor first_run as the step read it")
+        return self._step_record
+
+    def prepare_backward(self, input_grads: list, grad_wpd_out: torch.Tensor | None = None,
+                         grad_yaw_out: torch.Tensor | None = None,
+                         grad_rotation_body_direct: torch.Tensor | None = None, wrt=None) -> dict:
+        """The VJP of the last step's input preparation (srbd_prepare_inputs_backward): the 17 FP64
+        former-input cotangents (None entries: zero), optionally the float32 cotangents of the updated
+        world_position_desired / yaw_desired and the wrench's direct rotation_body term, -> float32 gradients
+        keyed by field name (wrt: names out of _native.PREP_GRAD_NAMES; None: all, without contact_table
+        when the schedule comes from set_gait)."""
+        rec = self._require_record("prepare_backward")
+        return solver.prepare_inputs_backward(rec.prep, list(input_grads), rec.N, rec.B, rec.fields(wrt),
+                                              grad_wpd_out, grad_yaw_out, grad_rotation_body_direct)
+
+    def backward(self, grad_wrench: torch.Tensor, grad_tau: torch.Tensor | None = None,
+                 contact_jacobian: torch.Tensor | None = None, contact_bool: torch.Tensor | None = None,
+                 wrt=None, status: torch.Tensor | None = None) -> dict:
+        """Gradients of a loss on the last step's foot wrench (B,2,6) -- and, with grad_tau (B,2,ndof),
+        contact_jacobian and contact_bool, on its stance torque -- with respect to the controller's own
+        float32 tensors, keyed by field name with the tensors' shapes (srbd_mpc_step_backward: wrench VJP,
+        adjoint KKT solve and former VJP, input-preparation VJP). wrt: field names (None: all 15, 14 under
+        set_gait). world_position_desired / yaw_desired are the values the step read. The step must have run
+        with cfg.keep_solution and cfg.differentiable, and the state estimate, command and parameter tensors
+        must still hold what it read (run_autograd keeps its own copies). The gradient is that of the
+        linearised KKT conditions at the returned iterate: exact at convergence.
+        status (int32 (B,), optional) receives the adjoint's status word."""
+        return self._require_record("backward").backward(grad_wrench, grad_tau, contact_jacobian, contact_bool, wrt,
+                                                         status)
+
+    def run_autograd(self, **overrides) -> torch.Tensor:
+        """One controller step as a differentiable function of the tensors given by keyword: each replaces
+        the controller's tensor of that name for this step (AUTOGRAD_FIELDS: the six state-estimate tensors,
+        the three command tensors, contact_table, dt_mpc, residual_lin_accel, residual_ang_accel). Returns
+        the foot wrench (B,2,6) as a fresh tensor; ``torch.autograd.grad(w.square().sum(), [a_lin, dt])``
+        then runs backward() on copies of everything it reads, so later steps do not invalidate the graph.
+        Needs cfg.keep_solution and cfg.differentiable; first derivatives only."""
+        if not (self.cfg.keep_solution and self.cfg.differentiable):
+            self._step_record = None
+            self._require_record("run_autograd")
+        unknown = [n for n in overrides if n not in AUTOGRAD_FIELDS]
+        if unknown:
+            raise ValueError(f"run_autograd: unknown field(s) {unknown}; allowed: {', '.join(AUTOGRAD_FIELDS)}")
+        if "contact_table" in overrides and self._gait is not None:
+            raise ValueError("run_autograd: contact_table is not read while the schedule comes from set_gait")
+        names = tuple(overrides)
+        return _MPCStepFunction.apply(self, names, *(overrides[n] for n in names))
+
     def run_three_kernel(self, J: torch.Tensor | None = None, cb: torch.Tensor | None = None):
         """The same step as three launches (srbd_prepare_inputs -> srbd_mpc_solve_fused ->
         srbd_u0_wrench_torque) with the 17 former inputs and the solution in device memory.
         Bit-identical to run() (tests/test_controller.py)."""
         N, B = self.horizon_length, self.num_envs
+        self._step_record = None  # not a differentiable step: no first_run snapshot is taken here
         self.prepare()
         out = solver.mpc_solve(self.former_inputs, N, self.cfg.pdipm_iterations, self.cfg.y0, self.buffers,
                                objective_f32=self.cost if self.cfg.compute_cost else None)
@@ -342,6 +420,66 @@ class MPCControllerHIP(BaseMPCController):
         keep: list = []
         self._step(self._prep_struct(keep), J, cb)
         return self.foot_wrench, self.cost, self.tau
+
+
+# the tensors run_autograd takes by keyword: every float32 input of the step but its own knot-point state
+AUTOGRAD_FIELDS = tuple(n for n in _native.PREP_GRAD_NAMES if n not in ("world_position_desired", "yaw_desired"))
+
+
+class _StepRecord:
+    """What the backward pass of one controller step reads: the step's constants (a copy of its MPCPrep), the
+    float32 tensors of it the derivative depends on, first_run as the step read it, the 17 former inputs and
+    the iterate the step wrote. A controller holds one of its live buffers; detached() copies them."""
+    READ = ("rotation_body", "desired_velocity_b", "desired_angular_velocity_b", "dt_mpc")
+
+    def __init__(self, p: _native.MPCPrep, tensors: dict, first_run_prev, former_inputs, iterate, N: int, B: int):
+        self.tensors = {n: tensors[n] for n in self.READ}
+        self.first_run_prev, self.former_inputs, self.iterate, self.N, self.B = first_run_prev, former_inputs, iterate, N, B
+        self.gait = bool(p.gait_phase)
+        self.prep = _native.MPCPrep.from_buffer_copy(p)
+        for n, t in self.tensors.items():
+            setattr(self.prep, n, t.data_ptr())
+        self.prep.first_run = first_run_prev.data_ptr()
+
+    def detached(self) -> "_StepRecord":
+        return _StepRecord(self.prep, {n: t.clone() for n, t in self.tensors.items()}, self.first_run_prev.clone(),
+                           [t.clone() for t in self.former_inputs], [t.clone() for t in self.iterate], self.N, self.B)
+
+    def fields(self, wrt) -> list:
+        if wrt is None:
+            return [n for n in _native.PREP_GRAD_NAMES if not (self.gait and n == "contact_table")]
+        return list(wrt)
+
+    def backward(self, grad_wrench, grad_tau=None, contact_jacobian=None, contact_bool=None, wrt=None,
+                 status=None) -> dict:
+        dev = self.former_inputs[0].device
+        conv = lambda t: None if t is None else _f32(t, dev)  # noqa: E731
+        return solver.mpc_step_backward(self.prep, self.former_inputs, self.iterate, conv(grad_wrench), self.N,
+                                        self.fields(wrt), conv(grad_tau), conv(contact_jacobian), conv(contact_bool),
+                                        status=status)
+
+
+class _MPCStepFunction(torch.autograd.Function):
+    """foot_wrench = step(overrides): forward one srbd_mpc_step launch, backward srbd_mpc_step_backward on
+    copies of what the step wrote."""
+
+    @staticmethod
+    def forward(ctx, ctrl, names, *tensors):
+        keep: list = []
+        p = ctrl._prep_struct(keep, overrides={n: t.detach() for n, t in zip(names, tensors)})
+        ctrl._step(p, None, None)
+        ctx.record = ctrl._step_record.detached()
+        ctx.names = names
+        ctx.like = [(t.shape, t.dtype) for t in tensors]
+        return ctrl.foot_wrench.clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_wrench):
+        wrt = [n for n, need in zip(ctx.names, ctx.needs_input_grad[2:]) if need]
+        got = ctx.record.backward(grad_wrench.contiguous(), wrt=wrt) if wrt else {}
+        return (None, None) + tuple(got[n].reshape(shape).to(dtype) if n in got else None
+                                    for n, (shape, dtype) in zip(ctx.names, ctx.like))
 
 
 # the reference's class name, for drop-in imports

@@ -931,6 +931,179 @@ int srbd_mpc_backward_multi(int horizon, int batch, int n_seeds, const double* c
                            grad_x_env_stride, workspace, input_grads, status, stream);
 }
 
+}  // extern "C"
+
+// ---- backward pass of the controller step's FP32 ends (mpc_io_backward.hpp; kernels in srbd_backward.hip,
+// the only unit that includes that header: the forward units' code does not change with it) ----
+
+namespace srbd {
+namespace bwd {
+void launch_prepare_backward(const PrepArgs& prep, const double* const* g, const float* gwpd, const float* gyaw,
+                             const double* gR, float* const* out, hipStream_t s);
+void launch_wrench_backward(int N, int batch, const double* x, const float* rotation_body, const float* grad_wrench,
+                            int ndof, const float* J, const float* contact, const float* grad_tau, double* grad_x,
+                            double* grad_R, hipStream_t s);
+}  // namespace bwd
+}  // namespace srbd
+
+namespace {
+
+// the former-input cotangents (bit i = former input i) each prep gradient reads: the table of
+// prepare_inputs_backward_kernel
+constexpr unsigned fin(int i) { return 1u << i; }
+constexpr unsigned kPrepGradDeps[SRBD_PREP_GRAD_COUNT] = {
+    fin(0) | fin(3),           // root_euler: x0, and the yaw knot point on a first run
+    fin(0) | fin(3) | fin(9),  // root_position: x0, x_ref's origin, body position
+    fin(0),                    // root_angular_velocity_w
+    fin(0),                    // root_velocity_w
+    fin(3) | fin(7) | fin(8),  // rotation_body: vw = R v_b in x_ref, R_body, I_world
+    fin(10) | fin(11),         // foot_position
+    fin(3),                    // desired_velocity_b
+    fin(3),                    // desired_angular_velocity_b
+    fin(3),                    // desired_height
+    fin(3),                    // world_position_desired
+    fin(3),                    // yaw_desired
+    fin(12),                   // contact_table
+    fin(3) | fin(4),           // dt_mpc
+    fin(15),                   // residual_lin_accel
+    fin(16),                   // residual_ang_accel
+};
+
+unsigned former_inputs_needed(unsigned prep_mask) {
+  unsigned need = 0;
+  for (int f = 0; f < SRBD_PREP_GRAD_COUNT; ++f)
+    if (prep_mask >> f & 1u) need |= kPrepGradDeps[f];
+  return need;
+}
+
+unsigned prep_request_mask(float* const* prep_grads) {
+  unsigned m = 0;
+  for (int f = 0; f < SRBD_PREP_GRAD_COUNT; ++f)
+    if (prep_grads[f]) m |= 1u << f;
+  return m;
+}
+
+int wrench_vjp_impl(const char* what, int horizon, int batch, const double* x, const float* rotation_body,
+                    const float* grad_wrench, int ndof, const float* contact_jacobian, const float* contact_bool,
+                    const float* grad_tau, double* grad_x, double* grad_rotation_body, void* stream) {
+  if (!horizon_ok(horizon) || batch < 0) return fail(what, "bad arguments");
+  if (grad_tau && (ndof < 1 || ndof > 64 || !contact_jacobian || !contact_bool))
+    return fail(what, "grad_tau needs contact_jacobian, contact_bool and ndof in 1..64");
+  if (batch == 0) return 0;
+  if (!x || !rotation_body || !grad_wrench || !grad_x) return fail(what, "null x / rotation_body / grad_wrench / grad_x");
+  srbd::bwd::launch_wrench_backward(horizon, batch, x, rotation_body, grad_wrench, grad_tau ? ndof : 0,
+                                    contact_jacobian, contact_bool, grad_tau, grad_x, grad_rotation_body,
+                                    (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : set_error((int)e, "u0_wrench_backward_kernel launch");
+}
+
+// the arrays of srbd_mpc_prep the prep VJP reads
+int check_prep_backward(const char* what, const srbd_mpc_prep* p) {
+  if (!p->rotation_body || !p->desired_velocity_b || !p->desired_angular_velocity_b || !p->dt_mpc || !p->first_run)
+    return fail(what, "null rotation_body / desired_velocity_b / desired_angular_velocity_b / dt_mpc / first_run");
+  return 0;
+}
+
+int prep_vjp_impl(const char* what, int horizon, int batch, const srbd_mpc_prep* p, const double* const* input_grads,
+                  const float* grad_wpd_out, const float* grad_yaw_out, const double* grad_rotation_body_direct,
+                  float* const* prep_grads, void* stream) {
+  if (!horizon_ok(horizon) || batch < 0 || !p || !input_grads || !prep_grads) return fail(what, "bad arguments");
+  if (p->gait_phase && prep_grads[SRBD_PREP_GRAD_CONTACT_TABLE])
+    return fail(what, "no contact_table gradient when the schedule comes from gait_phase");
+  if (batch == 0) return 0;
+  if (int rc = check_prep_backward(what, p)) return rc;
+  srbd::PrepArgs a{};  // only what the kernel reads
+  a.rotation_body = p->rotation_body;
+  a.des_vel_b = p->desired_velocity_b;
+  a.des_angvel_b = p->desired_angular_velocity_b;
+  a.dt_mpc = p->dt_mpc;
+  a.first_run = p->first_run;  // the pre-step snapshot; read only
+  std::memcpy(a.I_body, p->I_body, sizeof(a.I_body));
+  a.step_dt = p->step_dt;
+  a.literal = p->literal_layout ? 1 : 0;
+  a.N = horizon;
+  a.batch = batch;
+  srbd::bwd::launch_prepare_backward(a, input_grads, grad_wpd_out, grad_yaw_out, grad_rotation_body_direct,
+                                     prep_grads, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : set_error((int)e, "prepare_inputs_backward_kernel launch");
+}
+
+size_t former_in_width(int i, int N) { return (size_t)srbd::former_in_nnz(i, N); }
+
+}  // namespace
+
+extern "C" {
+
+int srbd_u0_wrench_backward(int horizon, int batch, const double* x, const float* rotation_body,
+                            const float* grad_wrench, int ndof, const float* contact_jacobian,
+                            const float* contact_bool, const float* grad_tau, double* grad_x,
+                            double* grad_rotation_body, void* stream) {
+  return wrench_vjp_impl("srbd_u0_wrench_backward", horizon, batch, x, rotation_body, grad_wrench, ndof,
+                         contact_jacobian, contact_bool, grad_tau, grad_x, grad_rotation_body, stream);
+}
+
+int srbd_prepare_inputs_backward(int horizon, int batch, const srbd_mpc_prep* prep, const double* const* input_grads,
+                                 const float* grad_wpd_out, const float* grad_yaw_out,
+                                 const double* grad_rotation_body_direct, float* const* prep_grads, void* stream) {
+  return prep_vjp_impl("srbd_prepare_inputs_backward", horizon, batch, prep, input_grads, grad_wpd_out, grad_yaw_out,
+                       grad_rotation_body_direct, prep_grads, stream);
+}
+
+unsigned srbd_prep_grad_deps(int field) {
+  return field >= 0 && field < SRBD_PREP_GRAD_COUNT ? kPrepGradDeps[field] : 0u;
+}
+
+size_t srbd_mpc_step_backward_workspace_doubles(int horizon, int batch, unsigned prep_mask) {
+  if (!horizon_ok(horizon) || batch < 0) return 0;
+  const unsigned need = former_inputs_needed(prep_mask ? prep_mask : ~0u);  // 0 = all 15
+  size_t per_env = 24 * (size_t)horizon + 9;  // the seed grad_x and the direct rotation_body term
+  for (int i = 0; i < 17; ++i)
+    if (need >> i & 1u) per_env += former_in_width(i, horizon);
+  // need == 0 would read as "all 17" there; every prep gradient reads some former input, so it is never 0
+  return (size_t)batch * per_env + srbd_mpc_backward_multi_workspace_doubles(horizon, batch, 1, need);
+}
+
+int srbd_mpc_step_backward(int horizon, int batch, const srbd_mpc_prep* prep, const double* const* former_inputs,
+                           const double* const* iterate, const float* grad_wrench, int ndof,
+                           const float* contact_jacobian, const float* contact_bool, const float* grad_tau,
+                           const float* grad_wpd_out, const float* grad_yaw_out, double* workspace,
+                           float* const* prep_grads, int* status, void* stream) {
+  const char* what = "srbd_mpc_step_backward";
+  if (!horizon_ok(horizon) || batch < 0 || !prep || !former_inputs || !iterate || !prep_grads)
+    return fail(what, "bad arguments");
+  if (grad_tau && (ndof < 1 || ndof > 64 || !contact_jacobian || !contact_bool))
+    return fail(what, "grad_tau needs contact_jacobian, contact_bool and ndof in 1..64");
+  if (prep->gait_phase && prep_grads[SRBD_PREP_GRAD_CONTACT_TABLE])
+    return fail(what, "no contact_table gradient when the schedule comes from gait_phase");
+  if (batch == 0) return 0;
+  const unsigned prep_mask = prep_request_mask(prep_grads);
+  if (prep_mask == 0) return fail(what, "no prep gradient requested");
+  if (!workspace || !grad_wrench || !iterate[0] || !iterate[1] || !iterate[2] || !iterate[3])
+    return fail(what, "null workspace / grad_wrench / iterate");
+  if (int rc = check_prep_backward(what, prep)) return rc;
+  const unsigned need = former_inputs_needed(prep_mask);
+  const size_t B = (size_t)batch;
+  double* seed = workspace;
+  double* direct = seed + B * 24 * (size_t)horizon;
+  double* o = direct + B * 9;
+  double* fin_grads[17];
+  for (int i = 0; i < 17; ++i) {
+    fin_grads[i] = (need >> i & 1u) ? o : nullptr;
+    if (fin_grads[i]) o += B * former_in_width(i, horizon);
+  }
+  const bool want_R = prep_grads[SRBD_PREP_GRAD_ROTATION_BODY] != nullptr;
+  if (int rc = wrench_vjp_impl(what, horizon, batch, iterate[0], prep->rotation_body, grad_wrench, ndof,
+                               contact_jacobian, contact_bool, grad_tau, seed, want_R ? direct : nullptr, stream))
+    return rc;
+  if (int rc = mpc_backward_impl(what, false, horizon, batch, 1, former_inputs, iterate, seed, 24 * (size_t)horizon, o,
+                                 fin_grads, status, stream))
+    return rc;
+  return prep_vjp_impl(what, horizon, batch, prep, fin_grads, grad_wpd_out, grad_yaw_out, want_R ? direct : nullptr,
+                       prep_grads, stream);
+}
+
 int srbd_pattern_ccs(int horizon, int which, int* colptr, int* rowind) {
   if (!horizon_ok(horizon) || !colptr || !rowind) return -1;
   constexpr srbd::Tables T = srbd::make_tables();

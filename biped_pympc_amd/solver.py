@@ -512,3 +512,117 @@ def mpc_solve_autograd(former_inputs: list[torch.Tensor], N: int, n_iter: int, y
     iterate: exact at convergence, and within 0.1-1 % of finite differences of the solve at 35
     iterations (DESIGN.md)."""
     return _MPCSolveFunction.apply(N, n_iter, float(y0), *former_inputs)
+
+
+# ---- backward pass of the controller step's FP32 ends (include/srbd_mpc.h: wrench cotangent -> FP32 inputs) ----
+
+def _f32_arg(t, shape, what: str, name: str):
+    """None, or a contiguous float32 CUDA tensor of `shape` on the current device -> its pointer."""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+        raise TypeError(f"{what}: {name} must be a CUDA float32 tensor")
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device.index != torch.cuda.current_device():
+        raise ValueError(f"{what}: {name} must be a contiguous {tuple(shape)} tensor on the current device, "
+                         f"got {tuple(t.shape)} on {t.device}")
+    return t.data_ptr()
+
+
+def _torque_cotangent(B: int, grad_tau, contact_jacobian, contact_bool, what: str):
+    """(ndof, J pointer, contact pointer, grad_tau pointer) of the optional stance-torque cotangent."""
+    if grad_tau is None:
+        return 0, None, None, None
+    if contact_jacobian is None or contact_bool is None:
+        raise ValueError(f"{what}: grad_tau needs contact_jacobian and contact_bool")
+    if grad_tau.dim() != 3 or grad_tau.shape[2] < 1:
+        raise ValueError(f"{what}: grad_tau must be ({B}, 2, ndof)")
+    ndof = grad_tau.shape[2]
+    return (ndof, _f32_arg(contact_jacobian, (B, 2, 6, ndof), what, "contact_jacobian"),
+            _f32_arg(contact_bool, (B, 2), what, "contact_bool"), _f32_arg(grad_tau, (B, 2, ndof), what, "grad_tau"))
+
+
+def u0_wrench_backward(x: torch.Tensor, rotation_body: torch.Tensor, grad_wrench: torch.Tensor, N: int,
+                       grad_tau: torch.Tensor | None = None, contact_jacobian: torch.Tensor | None = None,
+                       contact_bool: torch.Tensor | None = None, want_rotation: bool = True,
+                       grad_x: torch.Tensor | None = None):
+    """``srbd_u0_wrench_backward``: the VJP of the u0 -> foot wrench (-> stance torque) epilogue. ``x`` (B, 24N)
+    float64 the solution, ``rotation_body`` (B, 3, 3) and ``grad_wrench`` (B, 2, 6) float32; ``grad_tau``
+    (B, 2, ndof) float32 with ``contact_jacobian`` (B, 2, 6, ndof) and ``contact_bool`` (B, 2) adds the torque's
+    cotangent. Returns ``(grad_x, grad_rotation_body)``: (B, 24N) float64, zero outside the u0 block and at its
+    entries 6 and 9, and (B, 9) float64, the wrench's direct dependence on rotation_body (None without
+    ``want_rotation``)."""
+    what = "u0_wrench_backward"
+    B = x.shape[0]
+    _check_batch([x], [24 * N], B, what)
+    if grad_x is None:
+        grad_x = torch.empty((B, 24 * N), dtype=torch.float64, device=x.device)
+    _check_batch([grad_x], [24 * N], B, what + " grad_x")
+    gR = torch.empty((B, 9), dtype=torch.float64, device=x.device) if want_rotation else None
+    ndof, J, cb, gt = _torque_cotangent(B, grad_tau, contact_jacobian, contact_bool, what)
+    rc = _native.lib().srbd_u0_wrench_backward(
+        N, B, x.data_ptr(), _f32_arg(rotation_body, (B, 3, 3), what, "rotation_body"),
+        _f32_arg(grad_wrench, (B, 2, 6), what, "grad_wrench"), ndof, J, cb, gt, grad_x.data_ptr(),
+        None if gR is None else gR.data_ptr(), _stream_ptr())
+    _native.check(rc, "srbd_u0_wrench_backward")
+    return grad_x, gR
+
+
+def _prep_grad_outputs(B: int, N: int, wrt, device, what: str):
+    """wrt: names out of _native.PREP_GRAD_NAMES -> (dict name -> new float32 tensor, pointer array of 15, mask)."""
+    names = _native.PREP_GRAD_NAMES
+    unknown = [n for n in wrt if n not in names]
+    if unknown:
+        raise ValueError(f"{what}: unknown field(s) {unknown}; known: {', '.join(names)}")
+    out = {n: torch.empty((B,) + _native.prep_grad_shape(n, N), dtype=torch.float32, device=device)
+           for n in names if n in wrt}
+    if not out:
+        raise ValueError(f"{what}: no gradient requested")
+    mask = sum(1 << i for i, n in enumerate(names) if n in out)
+    return out, _native.ptr_array([out[n].data_ptr() if n in out else 0 for n in names]), mask
+
+
+def prepare_inputs_backward(prep, input_grads: list, N: int, B: int, wrt, grad_wpd_out: torch.Tensor | None = None,
+                            grad_yaw_out: torch.Tensor | None = None,
+                            grad_rotation_body_direct: torch.Tensor | None = None) -> dict:
+    """``srbd_prepare_inputs_backward``: the 17 FP64 former-input cotangents (None: zero) -> float32 gradients of
+    the controller tensors named in ``wrt`` (``_native.PREP_GRAD_NAMES``), as a dict. ``prep``: the
+    ``_native.MPCPrep`` of the step, its ``first_run`` the flag before the step."""
+    import ctypes
+    what = "prepare_inputs_backward"
+    _check_batch(input_grads, Dims(N).former_in_nnz, B, what)
+    _check_batch([grad_rotation_body_direct], [9], B, what + " grad_rotation_body_direct")
+    device = torch.device("cuda", torch.cuda.current_device())
+    out, ptrs, _ = _prep_grad_outputs(B, N, wrt, device, what)
+    rc = _native.lib().srbd_prepare_inputs_backward(
+        N, B, ctypes.byref(prep), _ptrs(input_grads), _f32_arg(grad_wpd_out, (B, 3), what, "grad_wpd_out"),
+        _f32_arg(grad_yaw_out, (B,), what, "grad_yaw_out"),
+        None if grad_rotation_body_direct is None else grad_rotation_body_direct.data_ptr(), ptrs, _stream_ptr())
+    _native.check(rc, "srbd_prepare_inputs_backward")
+    return out
+
+
+def mpc_step_backward(prep, former_inputs: list[torch.Tensor], iterate: list[torch.Tensor],
+                      grad_wrench: torch.Tensor, N: int, wrt, grad_tau: torch.Tensor | None = None,
+                      contact_jacobian: torch.Tensor | None = None, contact_bool: torch.Tensor | None = None,
+                      grad_wpd_out: torch.Tensor | None = None, grad_yaw_out: torch.Tensor | None = None,
+                      status: torch.Tensor | None = None, workspace: torch.Tensor | None = None) -> dict:
+    """``srbd_mpc_step_backward``: wrench VJP -> adjoint KKT solve and former VJP -> input-preparation VJP in one
+    call (the bits of the three calls), from what a controller step with ``keep_solution`` wrote. Only the
+    former-input cotangents the fields in ``wrt`` read are computed. Returns a dict of float32 gradients."""
+    import ctypes
+    what = "mpc_step_backward"
+    d = Dims(N)
+    B = former_inputs[0].shape[0]
+    _check_batch(former_inputs, d.former_in_nnz, B, what)
+    _check_batch(list(iterate), d.solver_in_nnz[6:], B, what + " iterate")
+    out, ptrs, mask = _prep_grad_outputs(B, N, wrt, grad_wrench.device, what)
+    L = _native.lib()
+    workspace = _workspace(workspace, L.srbd_mpc_step_backward_workspace_doubles(N, B, mask), grad_wrench.device, what)
+    ndof, J, cb, gt = _torque_cotangent(B, grad_tau, contact_jacobian, contact_bool, what)
+    rc = L.srbd_mpc_step_backward(
+        N, B, ctypes.byref(prep), _ptrs(former_inputs), _ptrs(iterate),
+        _f32_arg(grad_wrench, (B, 2, 6), what, "grad_wrench"), ndof, J, cb, gt,
+        _f32_arg(grad_wpd_out, (B, 3), what, "grad_wpd_out"), _f32_arg(grad_yaw_out, (B,), what, "grad_yaw_out"),
+        workspace.data_ptr(), ptrs, _check_status(status, B, what), _stream_ptr())
+    _native.check(rc, "srbd_mpc_step_backward")
+    return out

@@ -409,6 +409,88 @@ int srbd_mpc_backward_multi(int horizon, int batch, int n_seeds, const double* c
                             const double* const* iterate, const double* grad_x, size_t grad_x_env_stride,
                             double* workspace, double* const* input_grads, int* status, void* stream);
 
+/* ---- Backward pass of the controller step: wrench cotangent -> the controller's FP32 tensors ---------
+ * srbd_mpc_step maps the FP32 tensors of srbd_mpc_prep to the FP32 foot wrench (and stance torque). The
+ * entries above differentiate its middle, the QP, in FP64 coordinates; the two below differentiate its
+ * FP32 ends, and srbd_mpc_step_backward chains all three. Conventions as above: host arrays of device
+ * pointers, asynchronous on `stream`, no device allocation, batch == 0 returns 0, bad arguments return an
+ * error code and a srbd_last_error() message without touching the GPU.
+ *
+ * Arithmetic: the forward's FP32 values are widened to FP64; products and sums are FP64, not contracted,
+ * in a fixed order per entry; a gradient on an FP32 tensor is rounded once, at its store. The forward's
+ * selects (first_run, the stationary test |v_x| < 1e-2) are constants of the derivative. An env's
+ * gradients have the same bits at any batch size and position. */
+
+/* The VJP of srbd_u0_wrench_torque. x (B,24N) the solution, rotation_body (B,3,3) float32, grad_wrench
+ * (B,2,6) float32; grad_tau (B,2,ndof) float32 is optional and needs contact_jacobian, contact_bool and
+ * ndof in 1..64. Writes grad_x (B,24N) FP64 -- the whole row: zeros outside the u0 block [12N, 12N+12)
+ * and at its entries 6 and 9, which the forward zeroes -- and, when non-NULL, grad_rotation_body (B,9)
+ * FP64, the wrench's direct dependence on rotation_body. */
+int srbd_u0_wrench_backward(int horizon, int batch, const double* x, const float* rotation_body,
+                            const float* grad_wrench, int ndof, const float* contact_jacobian,
+                            const float* contact_bool, const float* grad_tau, double* grad_x,
+                            double* grad_rotation_body, void* stream);
+
+/* Indices of the 15 gradients of srbd_prepare_inputs_backward (prep_grads): the FP32 tensors of
+ * srbd_mpc_prep, each with its tensor's shape. */
+#define SRBD_PREP_GRAD_ROOT_EULER 0
+#define SRBD_PREP_GRAD_ROOT_POSITION 1
+#define SRBD_PREP_GRAD_ROOT_ANGULAR_VELOCITY_W 2
+#define SRBD_PREP_GRAD_ROOT_VELOCITY_W 3
+#define SRBD_PREP_GRAD_ROTATION_BODY 4
+#define SRBD_PREP_GRAD_FOOT_POSITION 5
+#define SRBD_PREP_GRAD_DESIRED_VELOCITY_B 6
+#define SRBD_PREP_GRAD_DESIRED_ANGULAR_VELOCITY_B 7
+#define SRBD_PREP_GRAD_DESIRED_HEIGHT 8
+#define SRBD_PREP_GRAD_WORLD_POSITION_DESIRED 9 /* the value the step read */
+#define SRBD_PREP_GRAD_YAW_DESIRED 10           /* the value the step read */
+#define SRBD_PREP_GRAD_CONTACT_TABLE 11         /* explicit-table mode only */
+#define SRBD_PREP_GRAD_DT_MPC 12
+#define SRBD_PREP_GRAD_RESIDUAL_LIN_ACCEL 13
+#define SRBD_PREP_GRAD_RESIDUAL_ANG_ACCEL 14
+#define SRBD_PREP_GRAD_COUNT 15
+
+/* The VJP of srbd_prepare_inputs: input_grads (17 FP64 cotangents of the former inputs, their order and
+ * widths; NULL = zero) -> prep_grads (15 float32 arrays indexed by SRBD_PREP_GRAD_*; NULL = skipped, and
+ * skipping changes no bit of the others). grad_wpd_out (B,3) / grad_yaw_out (B) float32, optional: the
+ * cotangents of the UPDATED world_position_desired / yaw_desired, for callers that unroll several steps.
+ * grad_rotation_body_direct (B,9) FP64, optional: srbd_u0_wrench_backward's, added before the one
+ * rounding. `prep` is read only, and only rotation_body, desired_velocity_b, desired_angular_velocity_b,
+ * dt_mpc, first_run, gait_phase (as a mode flag), I_body, step_dt and literal_layout of it (the other
+ * arrays may be NULL: the map is linear in them); first_run is the flag as it was BEFORE the forward
+ * step. With x_ref's cotangent gx[k,j] = input_grads[3][12k+j], S_j = sum_k gx[k,j], T_j = sum_k k gx[k,j]:
+ * dt_mpc gets g_4 + wz T_2 + vw0 T_3 + vw1 T_4, the residual accelerations g_15 and g_16, rotation_body
+ * the terms of vw = R v_b, R_body, I_world = R I_body R^T and the direct one (DESIGN.md 6c has the table).
+ * The contact_table gradient is refused (bad arguments) when prep->gait_phase != NULL: the schedule then
+ * comes from the gait phase, which is piecewise constant. */
+int srbd_prepare_inputs_backward(int horizon, int batch, const srbd_mpc_prep* prep,
+                                 const double* const* input_grads /* 17, NULL entry = zero */,
+                                 const float* grad_wpd_out, const float* grad_yaw_out,
+                                 const double* grad_rotation_body_direct,
+                                 float* const* prep_grads /* 15, NULL entry = skipped */, void* stream);
+
+/* Host-only: which former-input cotangents prep gradient `field` (SRBD_PREP_GRAD_*) reads, as a mask with
+ * bit i = former input i (0 for an index out of range):
+ *   root_euler <- 0, 3;  root_position <- 0, 3, 9;  the two root velocities <- 0;  rotation_body <- 3, 7, 8;
+ *   foot_position <- 10, 11;  the three command tensors and the two knot-point tensors <- 3;
+ *   contact_table <- 12;  dt_mpc <- 3, 4;  residual_lin_accel <- 15;  residual_ang_accel <- 16. */
+unsigned srbd_prep_grad_deps(int field);
+
+/* srbd_u0_wrench_backward -> srbd_mpc_backward -> srbd_prepare_inputs_backward in one call (same bits).
+ * srbd_mpc_backward is asked for only the former inputs that the requested prep gradients (non-NULL
+ * prep_grads entries; at least one) read. former_inputs and iterate (x, s, z, y) are what the step wrote
+ * (srbd_mpc_step with former_inputs and outputs); rotation_body is prep's. status (B ints, may be NULL)
+ * is the adjoint's. workspace: caller-owned device memory of srbd_mpc_step_backward_workspace_doubles
+ * doubles, prep_mask bit f = prep gradient f requested (0 = all 15; 0 doubles for bad arguments): the seed
+ * grad_x (B,24N), the direct rotation_body term (B,9), the former-input cotangents the requested prep
+ * gradients read, then srbd_mpc_backward_multi_workspace_doubles(horizon, batch, 1, those inputs). */
+size_t srbd_mpc_step_backward_workspace_doubles(int horizon, int batch, unsigned prep_mask /* 0 = all 15 */);
+int srbd_mpc_step_backward(int horizon, int batch, const srbd_mpc_prep* prep, const double* const* former_inputs,
+                           const double* const* iterate /* x, s, z, y */, const float* grad_wrench, int ndof,
+                           const float* contact_jacobian, const float* contact_bool, const float* grad_tau,
+                           const float* grad_wpd_out, const float* grad_yaw_out, double* workspace,
+                           float* const* prep_grads, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
