@@ -145,6 +145,13 @@ def lib() -> ctypes.CDLL:
     L.srbd_mpc_backward_multi.restype = ctypes.c_int
     L.srbd_mpc_backward_multi.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, P, P, _c_dp, ctypes.c_size_t,
                                           _c_dp, P, _c_dp, ctypes.c_void_p]
+    # cotangents of every output of a solve (x, s, z, y, objective): srbd_backward_seeds in place of grad_x
+    SP = ctypes.POINTER(BackwardSeeds)
+    L.srbd_pdipm_backward_seeds.restype = ctypes.c_int
+    L.srbd_pdipm_backward_seeds.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, P, SP, P, _c_dp, ctypes.c_void_p]
+    L.srbd_mpc_backward_seeds.restype = ctypes.c_int
+    L.srbd_mpc_backward_seeds.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, P, P, SP, _c_dp, P, _c_dp,
+                                          ctypes.c_void_p]
     # the backward pass of the controller step's FP32 ends: wrench / torque VJP, input-preparation VJP, the chain
     L.srbd_u0_wrench_backward.restype = ctypes.c_int
     L.srbd_u0_wrench_backward.argtypes = [ctypes.c_int, ctypes.c_int, _c_dp, _c_dp, _c_dp, ctypes.c_int, _c_dp, _c_dp,
@@ -159,6 +166,12 @@ def lib() -> ctypes.CDLL:
     L.srbd_mpc_step_backward.restype = ctypes.c_int
     L.srbd_mpc_step_backward.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(MPCPrep), P, P, _c_dp, ctypes.c_int,
                                          _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, P, _c_dp, ctypes.c_void_p]
+    # ... with the cotangent of the step's MPC cost (grad_cost after grad_wrench)
+    L.srbd_mpc_step_backward_cost_workspace_doubles.restype = ctypes.c_size_t
+    L.srbd_mpc_step_backward_cost_workspace_doubles.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint]
+    L.srbd_mpc_step_backward_cost.restype = ctypes.c_int
+    L.srbd_mpc_step_backward_cost.argtypes = (L.srbd_mpc_step_backward.argtypes[:6] + [_c_dp]
+                                              + L.srbd_mpc_step_backward.argtypes[6:])
     _lib = L
     return L
 
@@ -209,6 +222,16 @@ class MPCPrep(ctypes.Structure):
         ("I_body", ctypes.c_float * 9), ("mass", ctypes.c_double), ("mu", ctypes.c_double),
         ("Q", ctypes.c_float * 13), ("q_len", ctypes.c_int), ("R", ctypes.c_float * 12),
         ("step_dt", ctypes.c_float), ("literal_layout", ctypes.c_int)]
+
+
+class BackwardSeeds(ctypes.Structure):
+    """ctypes mirror of ``srbd_backward_seeds`` (include/srbd_mpc.h): the cotangents of a solve's outputs,
+    device pointers as void* (None: zero), and whether the seed rows are shared by every env."""
+    _fields_ = [("grad_x", _c_dp), ("grad_s", _c_dp), ("grad_z", _c_dp), ("grad_y", _c_dp),
+                ("grad_objective", _c_dp), ("shared", ctypes.c_int)]
+
+
+SEED_KINDS = ("x", "s", "z", "y", "objective")  # the outputs of a solve a cotangent may be given on
 
 
 class SolveInfo(ctypes.Structure):

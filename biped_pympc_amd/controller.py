@@ -347,11 +347,12 @@ class MPCControllerHIP(BaseMPCController):
         return solver.prepare_inputs_backward(rec.prep, list(input_grads), rec.N, rec.B, rec.fields(wrt),
                                               grad_wpd_out, grad_yaw_out, grad_rotation_body_direct)
 
-    def backward(self, grad_wrench: torch.Tensor, grad_tau: torch.Tensor | None = None,
+    def backward(self, grad_wrench: torch.Tensor | None = None, grad_tau: torch.Tensor | None = None,
                  contact_jacobian: torch.Tensor | None = None, contact_bool: torch.Tensor | None = None,
-                 wrt=None, status: torch.Tensor | None = None) -> dict:
+                 wrt=None, status: torch.Tensor | None = None, grad_cost: torch.Tensor | None = None) -> dict:
         """Gradients of a loss on the last step's foot wrench (B,2,6) -- and, with grad_tau (B,2,ndof),
-        contact_jacobian and contact_bool, on its stance torque -- with respect to the controller's own
+        contact_jacobian and contact_bool, on its stance torque, and, with grad_cost (B,), on its MPC cost
+        (cfg.compute_cost; grad_wrench may then be None) -- with respect to the controller's own
         float32 tensors, keyed by field name with the tensors' shapes (srbd_mpc_step_backward: wrench VJP,
         adjoint KKT solve and former VJP, input-preparation VJP). wrt: field names (None: all 15, 14 under
         set_gait). world_position_desired / yaw_desired are the values the step read. The step must have run
@@ -359,26 +360,34 @@ class MPCControllerHIP(BaseMPCController):
         must still hold what it read (run_autograd keeps its own copies). The gradient is that of the
         linearised KKT conditions at the returned iterate: exact at convergence.
         status (int32 (B,), optional) receives the adjoint's status word."""
+        if grad_cost is not None and not self.cfg.compute_cost:
+            raise RuntimeError("MPCControllerHIP.backward(grad_cost=...) needs cfg.compute_cost=True: without it "
+                               "the step computes no cost")
         return self._require_record("backward").backward(grad_wrench, grad_tau, contact_jacobian, contact_bool, wrt,
-                                                         status)
+                                                         status, grad_cost)
 
-    def run_autograd(self, **overrides) -> torch.Tensor:
+    def run_autograd(self, return_cost: bool = False, **overrides):
         """One controller step as a differentiable function of the tensors given by keyword: each replaces
         the controller's tensor of that name for this step (AUTOGRAD_FIELDS: the six state-estimate tensors,
         the three command tensors, contact_table, dt_mpc, residual_lin_accel, residual_ang_accel). Returns
         the foot wrench (B,2,6) as a fresh tensor; ``torch.autograd.grad(w.square().sum(), [a_lin, dt])``
         then runs backward() on copies of everything it reads, so later steps do not invalidate the graph.
+        With ``return_cost`` (needs cfg.compute_cost) it returns ``(wrench, cost)``, cost (B,) float32 the MPC
+        cost of the step, and ``torch.autograd.grad(cost.sum() + w.square().sum(), [a_lin, dt])`` works.
         Needs cfg.keep_solution and cfg.differentiable; first derivatives only."""
         if not (self.cfg.keep_solution and self.cfg.differentiable):
             self._step_record = None
             self._require_record("run_autograd")
+        if return_cost and not self.cfg.compute_cost:
+            raise RuntimeError("MPCControllerHIP.run_autograd(return_cost=True) needs cfg.compute_cost=True")
         unknown = [n for n in overrides if n not in AUTOGRAD_FIELDS]
         if unknown:
             raise ValueError(f"run_autograd: unknown field(s) {unknown}; allowed: {', '.join(AUTOGRAD_FIELDS)}")
         if "contact_table" in overrides and self._gait is not None:
             raise ValueError("run_autograd: contact_table is not read while the schedule comes from set_gait")
         names = tuple(overrides)
-        return _MPCStepFunction.apply(self, names, *(overrides[n] for n in names))
+        w, cost = _MPCStepFunction.apply(self, names, bool(return_cost), *(overrides[n] for n in names))
+        return (w, cost) if return_cost else w
 
     def run_three_kernel(self, J: torch.Tensor | None = None, cb: torch.Tensor | None = None):
         """The same step as three launches (srbd_prepare_inputs -> srbd_mpc_solve_fused ->
@@ -451,12 +460,12 @@ class _StepRecord:
         return list(wrt)
 
     def backward(self, grad_wrench, grad_tau=None, contact_jacobian=None, contact_bool=None, wrt=None,
-                 status=None) -> dict:
+                 status=None, grad_cost=None) -> dict:
         dev = self.former_inputs[0].device
         conv = lambda t: None if t is None else _f32(t, dev)  # noqa: E731
         return solver.mpc_step_backward(self.prep, self.former_inputs, self.iterate, conv(grad_wrench), self.N,
                                         self.fields(wrt), conv(grad_tau), conv(contact_jacobian), conv(contact_bool),
-                                        status=status)
+                                        status=status, grad_cost=conv(grad_cost))
 
 
 class _MPCStepFunction(torch.autograd.Function):
@@ -464,22 +473,29 @@ class _MPCStepFunction(torch.autograd.Function):
     copies of what the step wrote."""
 
     @staticmethod
-    def forward(ctx, ctrl, names, *tensors):
+    def forward(ctx, ctrl, names, with_cost, *tensors):
         keep: list = []
         p = ctrl._prep_struct(keep, overrides={n: t.detach() for n, t in zip(names, tensors)})
         ctrl._step(p, None, None)
         ctx.record = ctrl._step_record.detached()
         ctx.names = names
         ctx.like = [(t.shape, t.dtype) for t in tensors]
-        return ctrl.foot_wrench.clone()
+        ctx.set_materialize_grads(False)  # an unused output's cotangent stays None
+        cost = ctrl.cost.clone()
+        if not with_cost:
+            ctx.mark_non_differentiable(cost)
+        return ctrl.foot_wrench.clone(), cost
 
     @staticmethod
     @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_wrench):
-        wrt = [n for n, need in zip(ctx.names, ctx.needs_input_grad[2:]) if need]
-        got = ctx.record.backward(grad_wrench.contiguous(), wrt=wrt) if wrt else {}
-        return (None, None) + tuple(got[n].reshape(shape).to(dtype) if n in got else None
-                                    for n, (shape, dtype) in zip(ctx.names, ctx.like))
+    def backward(ctx, grad_wrench, grad_cost):
+        wrt = [n for n, need in zip(ctx.names, ctx.needs_input_grad[3:]) if need]
+        got = {}
+        if wrt and not (grad_wrench is None and grad_cost is None):
+            got = ctx.record.backward(None if grad_wrench is None else grad_wrench.contiguous(), wrt=wrt,
+                                      grad_cost=None if grad_cost is None else grad_cost.contiguous())
+        return (None, None, None) + tuple(got[n].reshape(shape).to(dtype) if n in got else None
+                                          for n, (shape, dtype) in zip(ctx.names, ctx.like))
 
 
 # the reference's class name, for drop-in imports

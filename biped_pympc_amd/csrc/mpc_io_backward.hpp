@@ -232,7 +232,16 @@ __global__ __launch_bounds__(256) void u0_wrench_backward_kernel(int N, int batc
     }
 }
 
+// The cotangent of the step's objective_f32 (B) widened to FP64 for the adjoint kernel: the one rounding of
+// J to float32 in the forward is read as the identity.
+__global__ __launch_bounds__(256) void widen_f32_kernel(int n, const float* __restrict__ src,
+                                                        double* __restrict__ dst) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e < n) dst[e] = (double)src[e];
+}
+
 namespace bwd {
+void launch_widen(int n, const float* src, double* dst, hipStream_t s);
 void launch_prepare_backward(const PrepArgs& prep, const double* const* g, const float* gwpd, const float* gyaw,
                              const double* gR, float* const* out, hipStream_t s);
 void launch_wrench_backward(int N, int batch, const double* x, const float* rotation_body, const float* grad_wrench,

@@ -14,6 +14,22 @@
 // full K, exactly as the forward kernel refines its directions. At a non-converged iterate the result
 // is the exact derivative of the linearised KKT conditions at that iterate (as in qpth).
 //
+// Seeds on the other outputs. A loss may also depend on s, z, y and on the QP objective
+// J = 1/2 x^T H x + f^T x (H without the regularisation). With cotangents g_x, g_s, g_z, g_y, g_J the
+// same matrix is solved for the full right-hand side,
+//   K [lx; ls; lz; ly] = [g~; g_s; g_z; g_y],   g~ = g_x + g_J (H o x + f),
+// in reduced form, with v = D^-1 (g_s - W g_z), D = 1 + dW:
+//   (H + bI + G^T Lam G) lx + A^T ly = g~ - G^T v,  A lx - d ly = g_y,  lz = v + Lam G lx,
+//   ls = g_z - G lx + d lz.
+// By the residual definitions e1..e4 of FastCtx::refine_rhs that is RX = -g~, R2 = g_s, RS = -g_z,
+// RE = -g_y and VV = DI (R2 + WD RS), formed after factor() (WD, DI are its results); solve(3),
+// refine_rhs() and solve(2) are unchanged. The six formulas below are unchanged too (ls enters none);
+// J's explicit dependence on H and f adds g_J (1/2 x[c] x[c]) to grad_H[c] and g_J x[c] to grad_f[c].
+// A null cotangent is zero: with only g_x given the kernels run the statements, and give the bits, of the
+// x-only form above. Each kernel has two instantiations: FULL = false takes g_x alone, with the other
+// cotangents compiled out (carrying their pointers and g_J across the solve costs the x-only path 3-4 %
+// in scalar-register spills); the host launches FULL = true when any other cotangent is given.
+//
 // Gradients, one value per CCS nonzero (every nonzero is its own parameter: nothing is summed over
 // stages), in qp_former's output order and widths:
 //   grad_H[c]     = -lx[c] x[c]                           (24N, H's pattern is its diagonal)
@@ -38,13 +54,32 @@ namespace srbd {
 
 constexpr int kStatusUnsupported = 8;  // include/srbd_mpc.h SRBD_STATUS_UNSUPPORTED
 
+// the cotangents of one solve's outputs, one row per seed; a null array is a zero cotangent
+struct BackwardSeeds {
+  const double *grad_x, *grad_s, *grad_z, *grad_y;  // rows of 24N, 16N, 16N, 14N
+  const double* grad_objective;                     // one double per row
+};
+
+// the other cotangents, at the end of the kernels' argument structs: the x-only instantiations never load them
+struct BackwardMoreSeeds {
+  const double *grad_s, *grad_z, *grad_y, *grad_objective;
+};
+
+// the seeds a kernel instantiation takes: all five (FULL), or grad_x alone with the rest null at compile time
+template <bool FULL>
+__device__ __forceinline__ BackwardSeeds seeds_taken(const double* grad_x, const BackwardMoreSeeds& more) {
+  if (FULL) return BackwardSeeds{grad_x, more.grad_s, more.grad_z, more.grad_y, more.grad_objective};
+  return BackwardSeeds{grad_x, nullptr, nullptr, nullptr, nullptr};
+}
+
 struct BackwardArgs {
-  const double* in[10];  // srbd_pdipm's inputs: Q_val, G_val, A_val, (f, h, b: not read), x, s, z, y
-  const double* grad_x;  // (B, 24N) dL/dx
+  const double* in[10];  // srbd_pdipm's inputs: Q_val, G_val, A_val, (f: with grad_objective; h, b: not read), x, s, z, y
+  const double* grad_x;  // (B, 24N) dL/dx, or null (FULL)
   double* out[6];        // grad_H, grad_f, grad_A, grad_b, grad_G, grad_d; null: not written
   int* status;           // (B) or null
   int N;
   int batch;
+  BackwardMoreSeeds more;  // rows of 16N, 16N, 14N and 1 per env
 };
 
 // FastLayout and, behind it, the saved lx / ly of the refinement step (the forward kernels park them
@@ -88,7 +123,64 @@ __device__ __forceinline__ double grad_diag(double lc, double xc) {
   return -(lc * xc);
 }
 
-template <int NT>  // as FastCtx: 0 = horizon at run time (the only instantiation, srbd_backward.hip)
+// the objective's direct terms: g_J d(1/2 x^T H x)/dH[c] and g_J d(f^T x)/df[c] added to the adjoint's
+__device__ __forceinline__ double add_objective_H(double base, double gJ, double xc) {
+#pragma clang fp contract(off)
+  const double h = 0.5 * xc, q = h * xc, t = gJ * q;
+  return base + t;
+}
+__device__ __forceinline__ double add_objective_f(double base, double gJ, double xc) {
+#pragma clang fp contract(off)
+  const double t = gJ * xc;
+  return base + t;
+}
+// VV = DI (R2 + WD RS), solve(3)'s D^-1 (r2 + W r_s)
+__device__ __forceinline__ double seed_vv(double di, double wd, double r2, double rs) {
+#pragma clang fp contract(off)
+  const double t = wd * rs, u = r2 + t;
+  return di * u;
+}
+
+// Seed row `row`'s right-hand side in FastCtx's residual convention: RX = -(g_x + g_J (H o x + f)),
+// R2 = g_s, RS = -g_z, RE = -g_y. VV = 0 here; seeded_vv() forms it once factor() has run. fg: this
+// env's f, read only with grad_objective. X and Hu must be in place.
+template <int NT>
+__device__ __forceinline__ void seed_rhs(FastCtx<NT>& C, const BackwardSeeds& sd, size_t row, const double* fg,
+                                         int N) {
+#pragma clang fp contract(off)
+  const int nz = 24 * N, m = 16 * N, p = 14 * N, lane = C.lane;
+  const double* gx = sd.grad_x ? sd.grad_x + row * nz : nullptr;
+  const double* gs = sd.grad_s ? sd.grad_s + row * m : nullptr;
+  const double* gz = sd.grad_z ? sd.grad_z + row * m : nullptr;
+  const double* gy = sd.grad_y ? sd.grad_y + row * p : nullptr;
+  const bool hasJ = sd.grad_objective != nullptr;
+  const double gJ = hasJ ? sd.grad_objective[row] : 0.0;
+  for (int e = lane; e < nz; e += 64) {
+    double g = gx ? gx[e] : 0.0;
+    if (hasJ) {
+      const double hx = C.Hu[(e < 12 * N ? 12 : 0) + e % 12] * C.X[e];  // Hu: [H_u | H_x]
+      const double dj = hx + fg[e], t = gJ * dj;
+      g = g + t;
+    }
+    C.RX[e] = -g;
+  }
+  for (int e = lane; e < m; e += 64) {
+    C.RS[e] = gz ? 0.0 - gz[e] : 0.0;
+    C.R2[e] = gs ? gs[e] : 0.0;
+    C.VV[e] = 0.0;
+  }
+  for (int e = lane; e < p; e += 64) C.RE[e] = gy ? 0.0 - gy[e] : 0.0;
+}
+
+// after factor(): entry q's R2 and RS were written by this lane (seed_rhs strides alike), and solve()
+// synchronises before it reads VV
+template <int NT>
+__device__ __forceinline__ void seeded_vv(FastCtx<NT>& C, const BackwardSeeds& sd, int N) {
+  if (!sd.grad_s && !sd.grad_z) return;  // VV stays 0
+  for (int q = C.lane; q < 16 * N; q += 64) C.VV[q] = seed_vv(C.DI[q], C.WD[q], C.R2[q], C.RS[q]);
+}
+
+template <int NT, bool FULL>  // NT as FastCtx: 0 = horizon at run time (the only one instantiated, srbd_backward.hip)
 __global__ __launch_bounds__(64) void pdipm_backward_kernel(BackwardArgs args) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int env = xcd_item(blockIdx.x, gridDim.x);
@@ -151,33 +243,48 @@ __global__ __launch_bounds__(64) void pdipm_backward_kernel(BackwardArgs args) {
   }
   C.constants(Ag[a_ubase(N) + c_tab.e6], Ag[a_ubase(N) + c_tab.e9]);
 
-  // ---- the iterate and the adjoint right-hand side [g; 0; 0; 0] ----
+  // ---- the iterate and the adjoint right-hand side [g~; g_s; g_z; g_y] ----
+  const BackwardSeeds sd = seeds_taken<FULL>(args.grad_x, args.more);
+  const bool hasJ = sd.grad_objective != nullptr;
+  const double gJ = hasJ ? sd.grad_objective[env] : 0.0;
   {
     const double* xg = args.in[6] + (size_t)env * nz;
     const double* sg = args.in[7] + (size_t)env * m;
     const double* zg = args.in[8] + (size_t)env * m;
     const double* yg = args.in[9] + (size_t)env * p;
-    const double* gg = args.grad_x + (size_t)env * nz;
-    for (int e = lane; e < nz; e += 64) {
-      C.X[e] = xg[e];
-      C.RX[e] = -gg[e];
-    }
-    for (int e = lane; e < m; e += 64) {
-      C.S[e] = sg[e];
-      C.Z[e] = zg[e];
-      C.RS[e] = 0.0;
-      C.R2[e] = 0.0;
-      C.VV[e] = 0.0;
-    }
-    for (int e = lane; e < p; e += 64) {
-      C.Y[e] = yg[e];
-      C.RE[e] = 0.0;
+    if (FULL) {
+      for (int e = lane; e < nz; e += 64) C.X[e] = xg[e];
+      for (int e = lane; e < m; e += 64) {
+        C.S[e] = sg[e];
+        C.Z[e] = zg[e];
+      }
+      for (int e = lane; e < p; e += 64) C.Y[e] = yg[e];
+      // seed_rhs reads X[e] on the lane that wrote it, and Hu (synchronised by constants())
+      seed_rhs(C, sd, (size_t)env, hasJ ? args.in[3] + (size_t)env * nz : nullptr, N);
+    } else {  // [g; 0; 0; 0]: seed_rhs's values, loaded in the iterate's loops
+      const double* gg = sd.grad_x + (size_t)env * nz;
+      for (int e = lane; e < nz; e += 64) {
+        C.X[e] = xg[e];
+        C.RX[e] = -gg[e];
+      }
+      for (int e = lane; e < m; e += 64) {
+        C.S[e] = sg[e];
+        C.Z[e] = zg[e];
+        C.RS[e] = 0.0;
+        C.R2[e] = 0.0;
+        C.VV[e] = 0.0;
+      }
+      for (int e = lane; e < p; e += 64) {
+        C.Y[e] = yg[e];
+        C.RE[e] = 0.0;
+      }
     }
   }
   __syncthreads();
 
   // ---- one factorisation, one solve, one refinement step against the full K ----
   C.factor();
+  seeded_vv(C, sd, N);
   C.solve(3, 0.0);
   C.refine_rhs();
   C.solve(2, 0.0);
@@ -191,8 +298,8 @@ __global__ __launch_bounds__(64) void pdipm_backward_kernel(BackwardArgs args) {
   bool nf = false;
   for (int e = lane; e < nz; e += 64) {
     nf = nf || not_finite(lx[e]);
-    if (oH) oH[e] = grad_diag(lx[e], C.X[e]);
-    if (of) of[e] = -lx[e];
+    if (oH) oH[e] = hasJ ? add_objective_H(grad_diag(lx[e], C.X[e]), gJ, C.X[e]) : grad_diag(lx[e], C.X[e]);
+    if (of) of[e] = hasJ ? add_objective_f(-lx[e], gJ, C.X[e]) : -lx[e];
   }
   if (oA)
     for (int e = lane; e < nA; e += 64) {
@@ -226,22 +333,23 @@ __global__ __launch_bounds__(64) void pdipm_backward_kernel(BackwardArgs args) {
 // step and the gradient epilogue run per seed. factor()'s results (WD, DI, PH, DV) are read-only to
 // solve() and refine_rhs() -- the forward kernel already runs two solves and two refinement solves per
 // factorisation -- so seed k's outputs have the bits pdipm_backward_kernel<0> gives for g_k alone.
-// Seed k of env e is read at grad_x + e * env_stride + k * 24N: env_stride = 0 shares one (M, 24N)
-// block among all envs (unit seeds: a Jacobian's rows), env_stride = M * 24N is a (B, M, 24N) tensor.
+// Seed k of env e is seed row e * M + k of every given cotangent array, or row k with `shared`: one
+// block of M rows for all envs (unit seeds: a Jacobian's rows) in place of (B, M, width) tensors.
 // Output o's row of (env e, seed k) is e * M + k. A QP that is not stage-invariant gets NaN in its M
 // rows; kStatusNonFinite reports a non-finite adjoint of any of the M seeds.
 struct BackwardMultiArgs {
   const double* in[10];  // as BackwardArgs
-  const double* grad_x;  // seeds, addressed as above
-  size_t env_stride;     // 0 or n_seeds * 24N (doubles)
+  const double* grad_x;  // seed rows of 24N, addressed as above, or null (FULL)
+  size_t shared;         // 1: M seed rows for all envs; 0: B * M
   double* out[6];        // (B, M, width) each; null: not written
   int* status;           // (B) or null
   int N;
   int batch;
   int n_seeds;           // M >= 1
+  BackwardMoreSeeds more;  // seed rows of 16N, 16N, 14N and 1, addressed alike
 };
 
-template <int NT>  // 0 = horizon at run time (the only instantiation, srbd_backward.hip)
+template <int NT, bool FULL>  // NT = 0: horizon at run time (the only one instantiated, srbd_backward.hip)
 __global__ __launch_bounds__(64) void pdipm_backward_multi_kernel(BackwardMultiArgs args) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int env = xcd_item(blockIdx.x, gridDim.x);
@@ -317,21 +425,19 @@ __global__ __launch_bounds__(64) void pdipm_backward_multi_kernel(BackwardMultiA
   __syncthreads();
   C.factor();
 
-  const double* seeds = args.grad_x + (size_t)env * args.env_stride;
+  const BackwardSeeds sd = seeds_taken<FULL>(args.grad_x, args.more);
+  const bool hasJ = sd.grad_objective != nullptr;
+  const double* fg = hasJ ? args.in[3] + (size_t)env * nz : nullptr;
   bool nf = false;
 #pragma unroll 1
   for (int k = 0; k < M; ++k) {
-    // ---- seed k's right-hand side [g_k; 0; 0; 0]: every array the solve, the refinement and the
+    // ---- seed k's right-hand side [g~_k; g_s; g_z; g_y]: every array the solve, the refinement and the
     // epilogue read is written here or by this seed's own solve (refine_rhs overwrites RX and RE,
     // solve(2) leaves its correction in VV, xsg / ysg are rewritten by refine_rhs) ----
-    const double* gg = seeds + (size_t)k * nz;
-    for (int e = lane; e < nz; e += 64) C.RX[e] = -gg[e];
-    for (int e = lane; e < m; e += 64) {
-      C.RS[e] = 0.0;
-      C.R2[e] = 0.0;
-      C.VV[e] = 0.0;
-    }
-    for (int e = lane; e < p; e += 64) C.RE[e] = 0.0;
+    const size_t srow = args.shared ? (size_t)k : row0 + (size_t)k;
+    const double gJ = hasJ ? sd.grad_objective[srow] : 0.0;
+    seed_rhs(C, sd, srow, fg, N);
+    seeded_vv(C, sd, N);
     __syncthreads();
 
     // ---- one solve and one refinement step against the full K ----
@@ -354,8 +460,8 @@ __global__ __launch_bounds__(64) void pdipm_backward_multi_kernel(BackwardMultiA
     const double *lx = C.TV, *lz = C.DZ;
     for (int e = lane; e < nz; e += 64) {
       nf = nf || not_finite(lx[e]);
-      if (oH) oH[e] = grad_diag(lx[e], C.X[e]);
-      if (of) of[e] = -lx[e];
+      if (oH) oH[e] = hasJ ? add_objective_H(grad_diag(lx[e], C.X[e]), gJ, C.X[e]) : grad_diag(lx[e], C.X[e]);
+      if (of) of[e] = hasJ ? add_objective_f(-lx[e], gJ, C.X[e]) : -lx[e];
     }
     if (oA)
       for (int e = lane; e < nA; e += 64) {
@@ -387,10 +493,11 @@ __global__ __launch_bounds__(64) void pdipm_backward_multi_kernel(BackwardMultiA
 
 namespace bwd {
 // host side of the backward translation unit (srbd_backward.hip)
-const void* adjoint_kernel();
-void launch_adjoint(const BackwardArgs& a, size_t lds, hipStream_t s);
-const void* adjoint_multi_kernel();
-void launch_adjoint_multi(const BackwardMultiArgs& a, size_t lds, hipStream_t s);
+// full: the instantiation that takes every cotangent; otherwise grad_x alone
+const void* adjoint_kernel(bool full);
+void launch_adjoint(const BackwardArgs& a, bool full, size_t lds, hipStream_t s);
+const void* adjoint_multi_kernel(bool full);
+void launch_adjoint_multi(const BackwardMultiArgs& a, bool full, size_t lds, hipStream_t s);
 }  // namespace bwd
 
 }  // namespace srbd

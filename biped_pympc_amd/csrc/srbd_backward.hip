@@ -13,16 +13,22 @@ namespace bwd {
 
 constexpr int kFormerWaves = 4;
 
-const void* adjoint_kernel() { return (const void*)pdipm_backward_kernel<0>; }
-
-void launch_adjoint(const BackwardArgs& a, size_t lds, hipStream_t s) {
-  hipLaunchKernelGGL(pdipm_backward_kernel<0>, dim3(a.batch), dim3(64), lds, s, a);
+const void* adjoint_kernel(bool full) {
+  return full ? (const void*)pdipm_backward_kernel<0, true> : (const void*)pdipm_backward_kernel<0, false>;
 }
 
-const void* adjoint_multi_kernel() { return (const void*)pdipm_backward_multi_kernel<0>; }
+void launch_adjoint(const BackwardArgs& a, bool full, size_t lds, hipStream_t s) {
+  if (full) hipLaunchKernelGGL((pdipm_backward_kernel<0, true>), dim3(a.batch), dim3(64), lds, s, a);
+  else hipLaunchKernelGGL((pdipm_backward_kernel<0, false>), dim3(a.batch), dim3(64), lds, s, a);
+}
 
-void launch_adjoint_multi(const BackwardMultiArgs& a, size_t lds, hipStream_t s) {
-  hipLaunchKernelGGL(pdipm_backward_multi_kernel<0>, dim3(a.batch), dim3(64), lds, s, a);
+const void* adjoint_multi_kernel(bool full) {
+  return full ? (const void*)pdipm_backward_multi_kernel<0, true> : (const void*)pdipm_backward_multi_kernel<0, false>;
+}
+
+void launch_adjoint_multi(const BackwardMultiArgs& a, bool full, size_t lds, hipStream_t s) {
+  if (full) hipLaunchKernelGGL((pdipm_backward_multi_kernel<0, true>), dim3(a.batch), dim3(64), lds, s, a);
+  else hipLaunchKernelGGL((pdipm_backward_multi_kernel<0, false>), dim3(a.batch), dim3(64), lds, s, a);
 }
 
 void launch_former_backward(const FormerBackwardArgs& a, hipStream_t s) {
@@ -48,6 +54,10 @@ void launch_wrench_backward(int N, int batch, const double* x, const float* rota
                             double* grad_R, hipStream_t s) {
   hipLaunchKernelGGL(u0_wrench_backward_kernel, dim3((batch + 255) / 256), dim3(256), 0, s, N, batch, x,
                      rotation_body, grad_wrench, ndof, J, contact, grad_tau, grad_x, grad_R);
+}
+
+void launch_widen(int n, const float* src, double* dst, hipStream_t s) {
+  hipLaunchKernelGGL(widen_f32_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, src, dst);
 }
 
 }  // namespace bwd

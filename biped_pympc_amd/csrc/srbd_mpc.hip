@@ -721,7 +721,8 @@ int srbd_mpc_step(int horizon, int n_iter, int batch, double y0, const srbd_mpc_
 
 // ---- backward pass (pdipm_backward.hpp, qp_former_backward.hpp; kernels in srbd_backward.hip) ----
 // One implementation per stage; the exported entries forward to them with their own name (`what`)
-// for the messages. A single-seed entry is n_seeds = 1 with the seeds' env stride 24 * horizon.
+// for the messages. A single-seed entry is n_seeds = 1 with the seeds' env stride 24 * horizon; an
+// x-only entry is a srbd_backward_seeds with grad_x alone (`x_only`: its messages name grad_x).
 
 namespace {
 
@@ -739,41 +740,56 @@ int check_seeds(const char* what, int horizon, int batch, int n_seeds, size_t en
   return 0;
 }
 
+// grad_x alone, addressed by the x-only entries' env stride (checked by check_seeds: 0 or n_seeds * 24N)
+srbd_backward_seeds x_seed(const double* grad_x, size_t env_stride) {
+  srbd_backward_seeds sd{};
+  sd.grad_x = grad_x;
+  sd.shared = env_stride == 0 ? 1 : 0;
+  return sd;
+}
+
+bool any_seed(const srbd_backward_seeds& sd) {
+  return sd.grad_x || sd.grad_s || sd.grad_z || sd.grad_y || sd.grad_objective;
+}
+
 // the adjoint KKT solve and the QP-data gradients of n_seeds seeds per env
-int adjoint_impl(const char* what, int horizon, int batch, int n_seeds, const double* const* inputs,
-                 const double* grad_x, size_t env_stride, double* const* qp_grads, int* status, void* stream) {
-  if (int rc = check_seeds(what, horizon, batch, n_seeds, env_stride, inputs && qp_grads)) return rc;
+int adjoint_impl(const char* what, bool x_only, int horizon, int batch, int n_seeds, const double* const* inputs,
+                 const srbd_backward_seeds& sd, double* const* qp_grads, int* status, void* stream) {
   if (batch == 0) return 0;
   for (int i = 0; i < 10; ++i)
-    if (!inputs[i] && !(i >= 3 && i <= 5)) return fail(what, "null input");  // f, h, b (3..5) are not read
-  if (!grad_x) return fail(what, "null grad_x");
+    if (!inputs[i] && !(i >= 3 && i <= 5)) return fail(what, "null input");  // f, h, b (3..5): see below
+  if (!any_seed(sd)) return fail(what, x_only ? "null grad_x" : "no seed given: all five cotangents are null");
+  if (sd.grad_objective && !inputs[3]) return fail(what, "grad_objective needs f (input 3)");
   const size_t lds = srbd::backward_lds_bytes(horizon);
   if (lds > 160 * 1024) return set_error(kErrInvalid, "horizon too large for the LDS-resident backward solve");
   auto fill = [&](auto& a) {  // the fields BackwardArgs and BackwardMultiArgs share
     for (int i = 0; i < 10; ++i) a.in[i] = inputs[i];
-    a.grad_x = grad_x;
+    a.grad_x = sd.grad_x;
+    a.more = srbd::BackwardMoreSeeds{sd.grad_s, sd.grad_z, sd.grad_y, sd.grad_objective};
     for (int i = 0; i < 6; ++i) a.out[i] = qp_grads[i];  // null: not written
     a.status = status;
     a.N = horizon;
     a.batch = batch;
   };
-  // one seed per env, (B, 24N): the single-seed kernel (the other's bits, 1-2 % faster there)
-  if (n_seeds == 1 && env_stride != 0) {
-    static srbd::LdsAttr cfg_backward;
+  // grad_x alone: the instantiation with the other cotangents compiled out (the same bits)
+  const bool full = sd.grad_s || sd.grad_z || sd.grad_y || sd.grad_objective;
+  // one seed per env, B rows: the single-seed kernel (the other's bits, 1-2 % faster there)
+  if (n_seeds == 1 && !sd.shared) {
+    static srbd::LdsAttr cfg_backward[2];
     srbd::BackwardArgs a{};
     fill(a);
-    if (int rc = ensure_lds_attr(srbd::bwd::adjoint_kernel(), lds, cfg_backward)) return rc;
-    srbd::bwd::launch_adjoint(a, lds, (hipStream_t)stream);
+    if (int rc = ensure_lds_attr(srbd::bwd::adjoint_kernel(full), lds, cfg_backward[full])) return rc;
+    srbd::bwd::launch_adjoint(a, full, lds, (hipStream_t)stream);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : set_error((int)e, "pdipm_backward_kernel launch");
   }
-  static srbd::LdsAttr cfg_backward_multi;
+  static srbd::LdsAttr cfg_backward_multi[2];
   srbd::BackwardMultiArgs a{};
   fill(a);
-  a.env_stride = env_stride;
+  a.shared = sd.shared ? 1 : 0;
   a.n_seeds = n_seeds;
-  if (int rc = ensure_lds_attr(srbd::bwd::adjoint_multi_kernel(), lds, cfg_backward_multi)) return rc;
-  srbd::bwd::launch_adjoint_multi(a, lds, (hipStream_t)stream);
+  if (int rc = ensure_lds_attr(srbd::bwd::adjoint_multi_kernel(full), lds, cfg_backward_multi[full])) return rc;
+  srbd::bwd::launch_adjoint_multi(a, full, lds, (hipStream_t)stream);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : set_error((int)e, "pdipm_backward_multi_kernel launch");
 }
@@ -842,14 +858,14 @@ void qp_widths(int horizon, size_t (&w)[6]) {  // H, f, A, b, G, d
 // input_grads read, (B, M, width) each; the others are null to both kernels (the adjoint kernel skips a
 // null output, the VJP reads a null gradient as zero). Whether asking for no gradient at all is an error
 // (`need_request`) is the calling entry's business.
-int mpc_backward_impl(const char* what, bool need_request, int horizon, int batch, int n_seeds,
-                      const double* const* former_inputs, const double* const* iterate, const double* grad_x,
-                      size_t env_stride, double* workspace, double* const* input_grads, int* status, void* stream) {
-  if (int rc = check_seeds(what, horizon, batch, n_seeds, env_stride, former_inputs && iterate && input_grads))
-    return rc;
+int mpc_backward_impl(const char* what, bool x_only, bool need_request, int horizon, int batch, int n_seeds,
+                      const double* const* former_inputs, const double* const* iterate,
+                      const srbd_backward_seeds& sd, double* workspace, double* const* input_grads, int* status,
+                      void* stream) {
   if (batch == 0) return 0;
-  if (!workspace || !grad_x || !iterate[0] || !iterate[1] || !iterate[2] || !iterate[3])
-    return fail(what, "null workspace / grad_x / iterate");
+  if (!workspace || (x_only && !sd.grad_x) || !iterate[0] || !iterate[1] || !iterate[2] || !iterate[3])
+    return fail(what, x_only ? "null workspace / grad_x / iterate" : "null workspace / iterate");
+  if (!any_seed(sd)) return fail(what, "no seed given: all five cotangents are null");
   unsigned input_mask = 0;
   for (int i = 0; i < 17; ++i)
     if (input_grads[i]) input_mask |= 1u << i;
@@ -871,7 +887,7 @@ int mpc_backward_impl(const char* what, bool need_request, int horizon, int batc
   }
   if (int rc = srbd_qp_former(horizon, batch, former_inputs, qp, stream)) return rc;
   const double* sin[10] = {qp[0], qp[4], qp[2], qp[1], qp[5], qp[3], iterate[0], iterate[1], iterate[2], iterate[3]};
-  if (int rc = adjoint_impl(what, horizon, batch, n_seeds, sin, grad_x, env_stride, gr, status, stream)) return rc;
+  if (int rc = adjoint_impl(what, x_only, horizon, batch, n_seeds, sin, sd, gr, status, stream)) return rc;
   return former_vjp_impl(what, horizon, batch, n_seeds, former_inputs, gr, input_grads, stream);
 }
 
@@ -879,15 +895,25 @@ int mpc_backward_impl(const char* what, bool need_request, int horizon, int batc
 
 int srbd_pdipm_backward(int horizon, int batch, const double* const* inputs, const double* grad_x,
                         double* const* qp_grads, int* status, void* stream) {
-  return adjoint_impl("srbd_pdipm_backward", horizon, batch, 1, inputs, grad_x, 24 * (size_t)horizon, qp_grads,
-                      status, stream);
+  const char* what = "srbd_pdipm_backward";
+  if (int rc = check_seeds(what, horizon, batch, 1, 24 * (size_t)horizon, inputs && qp_grads)) return rc;
+  return adjoint_impl(what, true, horizon, batch, 1, inputs, x_seed(grad_x, 24 * (size_t)horizon), qp_grads, status, stream);
 }
 
 int srbd_pdipm_backward_multi(int horizon, int batch, int n_seeds, const double* const* inputs,
                               const double* grad_x, size_t grad_x_env_stride, double* const* qp_grads,
                               int* status, void* stream) {
-  return adjoint_impl("srbd_pdipm_backward_multi", horizon, batch, n_seeds, inputs, grad_x, grad_x_env_stride,
-                      qp_grads, status, stream);
+  const char* what = "srbd_pdipm_backward_multi";
+  if (int rc = check_seeds(what, horizon, batch, n_seeds, grad_x_env_stride, inputs && qp_grads)) return rc;
+  return adjoint_impl(what, true, horizon, batch, n_seeds, inputs, x_seed(grad_x, grad_x_env_stride), qp_grads,
+                      status, stream);
+}
+
+int srbd_pdipm_backward_seeds(int horizon, int batch, int n_seeds, const double* const* inputs,
+                              const srbd_backward_seeds* seeds, double* const* qp_grads, int* status, void* stream) {
+  const char* what = "srbd_pdipm_backward_seeds";
+  if (int rc = check_seeds(what, horizon, batch, n_seeds, 0, inputs && seeds && qp_grads)) return rc;
+  return adjoint_impl(what, false, horizon, batch, n_seeds, inputs, *seeds, qp_grads, status, stream);
 }
 
 int srbd_qp_former_backward(int horizon, int batch, const double* const* former_inputs,
@@ -920,15 +946,32 @@ size_t srbd_mpc_backward_workspace_doubles(int horizon, int batch) {
 int srbd_mpc_backward(int horizon, int batch, const double* const* former_inputs, const double* const* iterate,
                       const double* grad_x, double* workspace, double* const* input_grads, int* status,
                       void* stream) {  // all 17 input_grads may be null: only `status` is written then
-  return mpc_backward_impl("srbd_mpc_backward", false, horizon, batch, 1, former_inputs, iterate, grad_x,
-                           24 * (size_t)horizon, workspace, input_grads, status, stream);
+  const char* what = "srbd_mpc_backward";
+  if (int rc = check_seeds(what, horizon, batch, 1, 24 * (size_t)horizon, former_inputs && iterate && input_grads))
+    return rc;
+  return mpc_backward_impl(what, true, false, horizon, batch, 1, former_inputs, iterate, x_seed(grad_x, 24 * (size_t)horizon),
+                           workspace, input_grads, status, stream);
 }
 
 int srbd_mpc_backward_multi(int horizon, int batch, int n_seeds, const double* const* former_inputs,
                             const double* const* iterate, const double* grad_x, size_t grad_x_env_stride,
                             double* workspace, double* const* input_grads, int* status, void* stream) {
-  return mpc_backward_impl("srbd_mpc_backward_multi", true, horizon, batch, n_seeds, former_inputs, iterate, grad_x,
-                           grad_x_env_stride, workspace, input_grads, status, stream);
+  const char* what = "srbd_mpc_backward_multi";
+  if (int rc = check_seeds(what, horizon, batch, n_seeds, grad_x_env_stride, former_inputs && iterate && input_grads))
+    return rc;
+  return mpc_backward_impl(what, true, true, horizon, batch, n_seeds, former_inputs, iterate,
+                           x_seed(grad_x, grad_x_env_stride), workspace, input_grads, status, stream);
+}
+
+// All 17 input_grads may be null (only `status` is written then), as in srbd_mpc_backward.
+int srbd_mpc_backward_seeds(int horizon, int batch, int n_seeds, const double* const* former_inputs,
+                            const double* const* iterate, const srbd_backward_seeds* seeds, double* workspace,
+                            double* const* input_grads, int* status, void* stream) {
+  const char* what = "srbd_mpc_backward_seeds";
+  if (int rc = check_seeds(what, horizon, batch, n_seeds, 0, former_inputs && iterate && seeds && input_grads))
+    return rc;
+  return mpc_backward_impl(what, false, false, horizon, batch, n_seeds, former_inputs, iterate, *seeds, workspace,
+                           input_grads, status, stream);
 }
 
 }  // extern "C"
@@ -943,6 +986,7 @@ void launch_prepare_backward(const PrepArgs& prep, const double* const* g, const
 void launch_wrench_backward(int N, int batch, const double* x, const float* rotation_body, const float* grad_wrench,
                             int ndof, const float* J, const float* contact, const float* grad_tau, double* grad_x,
                             double* grad_R, hipStream_t s);
+void launch_widen(int n, const float* src, double* dst, hipStream_t s);
 }  // namespace bwd
 }  // namespace srbd
 
@@ -1065,12 +1109,17 @@ size_t srbd_mpc_step_backward_workspace_doubles(int horizon, int batch, unsigned
   return (size_t)batch * per_env + srbd_mpc_backward_multi_workspace_doubles(horizon, batch, 1, need);
 }
 
-int srbd_mpc_step_backward(int horizon, int batch, const srbd_mpc_prep* prep, const double* const* former_inputs,
-                           const double* const* iterate, const float* grad_wrench, int ndof,
-                           const float* contact_jacobian, const float* contact_bool, const float* grad_tau,
-                           const float* grad_wpd_out, const float* grad_yaw_out, double* workspace,
-                           float* const* prep_grads, int* status, void* stream) {
-  const char* what = "srbd_mpc_step_backward";
+}  // extern "C"
+
+namespace {
+
+// wrench VJP (with grad_wrench) and the widened cost cotangent (with grad_cost) -> adjoint and former VJP
+// -> input-preparation VJP. `with_cost`: the entry takes grad_cost, and grad_wrench may then be null.
+int step_backward_impl(const char* what, bool with_cost, int horizon, int batch, const srbd_mpc_prep* prep,
+                       const double* const* former_inputs, const double* const* iterate, const float* grad_wrench,
+                       const float* grad_cost, int ndof, const float* contact_jacobian, const float* contact_bool,
+                       const float* grad_tau, const float* grad_wpd_out, const float* grad_yaw_out,
+                       double* workspace, float* const* prep_grads, int* status, void* stream) {
   if (!horizon_ok(horizon) || batch < 0 || !prep || !former_inputs || !iterate || !prep_grads)
     return fail(what, "bad arguments");
   if (grad_tau && (ndof < 1 || ndof > 64 || !contact_jacobian || !contact_bool))
@@ -1080,8 +1129,10 @@ int srbd_mpc_step_backward(int horizon, int batch, const srbd_mpc_prep* prep, co
   if (batch == 0) return 0;
   const unsigned prep_mask = prep_request_mask(prep_grads);
   if (prep_mask == 0) return fail(what, "no prep gradient requested");
-  if (!workspace || !grad_wrench || !iterate[0] || !iterate[1] || !iterate[2] || !iterate[3])
-    return fail(what, "null workspace / grad_wrench / iterate");
+  if (!workspace || (!with_cost && !grad_wrench) || !iterate[0] || !iterate[1] || !iterate[2] || !iterate[3])
+    return fail(what, with_cost ? "null workspace / iterate" : "null workspace / grad_wrench / iterate");
+  if (!grad_wrench && !grad_cost) return fail(what, "grad_wrench and grad_cost are both null");
+  if (grad_tau && !grad_wrench) return fail(what, "grad_tau needs grad_wrench");
   if (int rc = check_prep_backward(what, prep)) return rc;
   const unsigned need = former_inputs_needed(prep_mask);
   const size_t B = (size_t)batch;
@@ -1093,15 +1144,58 @@ int srbd_mpc_step_backward(int horizon, int batch, const srbd_mpc_prep* prep, co
     fin_grads[i] = (need >> i & 1u) ? o : nullptr;
     if (fin_grads[i]) o += B * former_in_width(i, horizon);
   }
-  const bool want_R = prep_grads[SRBD_PREP_GRAD_ROTATION_BODY] != nullptr;
-  if (int rc = wrench_vjp_impl(what, horizon, batch, iterate[0], prep->rotation_body, grad_wrench, ndof,
-                               contact_jacobian, contact_bool, grad_tau, seed, want_R ? direct : nullptr, stream))
-    return rc;
-  if (int rc = mpc_backward_impl(what, false, horizon, batch, 1, former_inputs, iterate, seed, 24 * (size_t)horizon, o,
+  // the wrench's direct rotation_body term exists only with a wrench cotangent
+  const bool want_R = grad_wrench && prep_grads[SRBD_PREP_GRAD_ROTATION_BODY] != nullptr;
+  srbd_backward_seeds sd{};
+  if (grad_wrench) {
+    if (int rc = wrench_vjp_impl(what, horizon, batch, iterate[0], prep->rotation_body, grad_wrench, ndof,
+                                 contact_jacobian, contact_bool, grad_tau, seed, want_R ? direct : nullptr, stream))
+      return rc;
+    sd.grad_x = seed;
+  }
+  double* mpc_ws = o;
+  if (grad_cost) {  // behind srbd_mpc_step_backward's layout: the cost cotangent, widened (B)
+    double* gJ = o + srbd_mpc_backward_multi_workspace_doubles(horizon, batch, 1, need);
+    srbd::bwd::launch_widen(batch, grad_cost, gJ, (hipStream_t)stream);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_error((int)e, "widen_f32_kernel launch");
+    sd.grad_objective = gJ;
+  }
+  if (int rc = mpc_backward_impl(what, !with_cost, false, horizon, batch, 1, former_inputs, iterate, sd, mpc_ws,
                                  fin_grads, status, stream))
     return rc;
   return prep_vjp_impl(what, horizon, batch, prep, fin_grads, grad_wpd_out, grad_yaw_out, want_R ? direct : nullptr,
                        prep_grads, stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int srbd_mpc_step_backward(int horizon, int batch, const srbd_mpc_prep* prep, const double* const* former_inputs,
+                           const double* const* iterate, const float* grad_wrench, int ndof,
+                           const float* contact_jacobian, const float* contact_bool, const float* grad_tau,
+                           const float* grad_wpd_out, const float* grad_yaw_out, double* workspace,
+                           float* const* prep_grads, int* status, void* stream) {
+  return step_backward_impl("srbd_mpc_step_backward", false, horizon, batch, prep, former_inputs, iterate,
+                            grad_wrench, nullptr, ndof, contact_jacobian, contact_bool, grad_tau, grad_wpd_out,
+                            grad_yaw_out, workspace, prep_grads, status, stream);
+}
+
+size_t srbd_mpc_step_backward_cost_workspace_doubles(int horizon, int batch, unsigned prep_mask) {
+  if (!horizon_ok(horizon) || batch < 0) return 0;
+  return srbd_mpc_step_backward_workspace_doubles(horizon, batch, prep_mask) + (size_t)batch;
+}
+
+int srbd_mpc_step_backward_cost(int horizon, int batch, const srbd_mpc_prep* prep,
+                                const double* const* former_inputs, const double* const* iterate,
+                                const float* grad_wrench, const float* grad_cost, int ndof,
+                                const float* contact_jacobian, const float* contact_bool, const float* grad_tau,
+                                const float* grad_wpd_out, const float* grad_yaw_out, double* workspace,
+                                float* const* prep_grads, int* status, void* stream) {
+  return step_backward_impl("srbd_mpc_step_backward_cost", true, horizon, batch, prep, former_inputs, iterate,
+                            grad_wrench, grad_cost, ndof, contact_jacobian, contact_bool, grad_tau, grad_wpd_out,
+                            grad_yaw_out, workspace, prep_grads, status, stream);
 }
 
 int srbd_pattern_ccs(int horizon, int which, int* colptr, int* rowind) {

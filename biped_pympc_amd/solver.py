@@ -6,6 +6,7 @@ Tensors are batched row-major ``(B, nnz)`` FP64 on the GPU, exactly the CusADi l
 """
 from __future__ import annotations
 
+import ctypes
 
 import torch
 
@@ -231,7 +232,7 @@ def mpc_solve(former_inputs: list[torch.Tensor], N: int, n_iter: int, y0: float 
     return buffers.outputs
 
 
-# ---- backward pass: gradients of a loss L(x) through the QP solve and the former ----
+# ---- backward pass: gradients of a loss on a solve's outputs through the QP solve and the former ----
 
 def _optional_outputs(outputs, widths, B: int, device, what: str, M: int | None = None, want=None):
     """(B, width) outputs, or (B, M, width) for M seeds: None -> those in `want` (default all)
@@ -261,10 +262,61 @@ def _workspace(workspace, n: int, device, what: str) -> torch.Tensor:
     return workspace
 
 
-def pdipm_backward(qp: list, iterate: list[torch.Tensor], grad_x: torch.Tensor, N: int,
-                   status: torch.Tensor | None = None, outputs: list | None = None):
+def _seed_widths(N: int) -> tuple:
+    return (24 * N, 16 * N, 16 * N, 14 * N, 1)  # x, s, z, y, objective
+
+
+def _seed_struct(seeds, B: int, N: int, what: str, multi: bool):
+    """The five cotangents (grad_x, grad_s, grad_z, grad_y, grad_objective; None: zero) -> (the C-ABI's
+    ``srbd_backward_seeds``, M). Single form: each holds B rows of its width (grad_objective (B,) or (B, 1)).
+    Multi form: every given one is (M, width), shared by every env, or (B, M, width), with one M and one
+    sharing for all (grad_objective: (M, 1) or (B, M, 1))."""
+    names = ["grad_" + k for k in _native.SEED_KINDS]
+    if all(t is None for t in seeds):
+        raise ValueError(f"{what}: no seed given ({', '.join(names)} are all None)")
+    M, shared = 1, None
+    for t, w, name in zip(seeds, _seed_widths(N), names):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64:
+            raise TypeError(f"{what}: {name} must be a CUDA float64 tensor")
+        if t.device.index != torch.cuda.current_device():
+            raise ValueError(f"{what}: {name} is on {t.device}, the current device is cuda:{torch.cuda.current_device()}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous")
+        if not multi:
+            if t.numel() != B * w or t.shape[0] != B:
+                raise ValueError(f"{what}: {name} must be ({B}, {w}), got {tuple(t.shape)}")
+            continue
+        if t.dim() == 2 and t.shape[1] == w and t.shape[0] >= 1:
+            m_t, sh_t = t.shape[0], True
+        elif t.dim() == 3 and t.shape[0] == B and t.shape[2] == w and t.shape[1] >= 1:
+            m_t, sh_t = t.shape[1], False
+        else:
+            raise ValueError(f"{what}: {name} must be (M, {w}) (shared by every env) or ({B}, M, {w}), M >= 1, "
+                             f"got {tuple(t.shape)}")
+        if shared is None:
+            M, shared = m_t, sh_t
+        elif (m_t, sh_t) != (M, shared):
+            raise ValueError(f"{what}: every seed must have the same M and the same sharing; {name} is "
+                             f"{tuple(t.shape)}")
+    sd = _native.BackwardSeeds(*[None if t is None else t.data_ptr() for t in seeds], 1 if shared else 0)
+    return sd, M
+
+
+def _only_x(seeds) -> bool:
+    return seeds[0] is not None and all(t is None for t in seeds[1:])
+
+
+def pdipm_backward(qp: list, iterate: list[torch.Tensor], grad_x: torch.Tensor | None, N: int,
+                   status: torch.Tensor | None = None, outputs: list | None = None, *,
+                   grad_s: torch.Tensor | None = None, grad_z: torch.Tensor | None = None,
+                   grad_y: torch.Tensor | None = None, grad_objective: torch.Tensor | None = None):
     """The adjoint KKT solve at ``iterate`` = [x, s, z, y] of the QP ``qp`` = [Q_val, G_val, A_val, f, h, b]
-    (f, h, b are not read and may be None) for the seed ``grad_x`` = dL/dx (B, 24N).
+    (h, b are not read and may be None; f only with ``grad_objective``) for the seed ``grad_x`` = dL/dx
+    (B, 24N) and, optionally, the cotangents of the solve's other outputs: ``grad_s`` and ``grad_z`` (B, 16N),
+    ``grad_y`` (B, 14N) and ``grad_objective`` (B,), that of J = 0.5 x^T H x + f^T x. A None seed is zero
+    (``grad_x`` may be None when another is given); with ``grad_x`` alone the result has today's bits.
 
     Returns [grad_H, grad_f, grad_A, grad_b, grad_G, grad_d] in qp_former's output order and CCS widths
     (every nonzero is its own parameter). ``outputs``: preallocated tensors, None entries are skipped.
@@ -272,14 +324,22 @@ def pdipm_backward(qp: list, iterate: list[torch.Tensor], grad_x: torch.Tensor, 
     (its gradients are NaN), STATUS_NONFINITE for a non-finite adjoint. The gradient at a non-converged
     iterate is the exact derivative of the linearised KKT conditions at that iterate (as in qpth)."""
     d = Dims(N)
-    B = grad_x.shape[0]
+    B = iterate[0].shape[0]
+    seeds = [grad_x, grad_s, grad_z, grad_y, grad_objective]
     ins = list(qp) + list(iterate)
     _check_batch(ins + [grad_x], d.solver_in_nnz + (d.nz,), B, "pdipm_backward")
     _require_qp_and_iterate(ins, "pdipm_backward")
-    outs = _optional_outputs(outputs, d.former_out_nnz, B, grad_x.device, "pdipm_backward outputs")
+    outs = _optional_outputs(outputs, d.former_out_nnz, B, iterate[0].device, "pdipm_backward outputs")
     st = _check_status(status, B, "pdipm_backward")
-    rc = _native.lib().srbd_pdipm_backward(N, B, _ptrs(ins), grad_x.data_ptr(), _ptrs(outs), st, _stream_ptr())
-    _native.check(rc, "srbd_pdipm_backward")
+    if _only_x(seeds):
+        rc = _native.lib().srbd_pdipm_backward(N, B, _ptrs(ins), grad_x.data_ptr(), _ptrs(outs), st, _stream_ptr())
+        _native.check(rc, "srbd_pdipm_backward")
+        return outs
+    sd, _ = _seed_struct(seeds, B, N, "pdipm_backward", multi=False)
+    if grad_objective is not None and ins[3] is None:
+        raise ValueError("pdipm_backward: grad_objective needs f (qp[3])")
+    rc = _native.lib().srbd_pdipm_backward_seeds(N, B, 1, _ptrs(ins), ctypes.byref(sd), _ptrs(outs), st, _stream_ptr())
+    _native.check(rc, "srbd_pdipm_backward_seeds")
     return outs
 
 
@@ -299,24 +359,35 @@ def qp_former_backward(former_inputs: list[torch.Tensor], qp_grads: list, N: int
     return outs
 
 
-def mpc_backward(former_inputs: list[torch.Tensor], iterate: list[torch.Tensor], grad_x: torch.Tensor, N: int,
+def mpc_backward(former_inputs: list[torch.Tensor], iterate: list[torch.Tensor], grad_x: torch.Tensor | None, N: int,
                  status: torch.Tensor | None = None, outputs: list | None = None,
-                 workspace: torch.Tensor | None = None):
+                 workspace: torch.Tensor | None = None, *, grad_s: torch.Tensor | None = None,
+                 grad_z: torch.Tensor | None = None, grad_y: torch.Tensor | None = None,
+                 grad_objective: torch.Tensor | None = None):
     """``srbd_mpc_backward``: qp_former -> pdipm_backward -> qp_former_backward in one call (same bits),
-    from the former inputs, the iterate [x, s, z, y] of the solve and ``grad_x``. Returns the gradients of
+    from the former inputs, the iterate [x, s, z, y] of the solve and ``grad_x`` -- and, optionally, the
+    cotangents of s, z, y and of the objective (the MPC cost), as ``pdipm_backward``. Returns the gradients of
     the 17 former inputs (``outputs``: preallocated tensors, None entries are skipped). ``workspace``:
     float64, srbd_mpc_backward_workspace_doubles(N, B) elements (allocated when None)."""
     d = Dims(N)
     B = former_inputs[0].shape[0]
+    dev = former_inputs[0].device
+    seeds = [grad_x, grad_s, grad_z, grad_y, grad_objective]
     _check_batch(former_inputs, d.former_in_nnz, B, "mpc_backward")
     _check_batch(list(iterate) + [grad_x], d.solver_in_nnz[6:] + (d.nz,), B, "mpc_backward iterate")
-    outs = _optional_outputs(outputs, d.former_in_nnz, B, grad_x.device, "mpc_backward outputs")
+    outs = _optional_outputs(outputs, d.former_in_nnz, B, dev, "mpc_backward outputs")
     L = _native.lib()
-    workspace = _workspace(workspace, L.srbd_mpc_backward_workspace_doubles(N, B), grad_x.device, "mpc_backward")
+    workspace = _workspace(workspace, L.srbd_mpc_backward_workspace_doubles(N, B), dev, "mpc_backward")
     st = _check_status(status, B, "mpc_backward")
-    rc = L.srbd_mpc_backward(N, B, _ptrs(former_inputs), _ptrs(iterate), grad_x.data_ptr(), workspace.data_ptr(),
-                             _ptrs(outs), st, _stream_ptr())
-    _native.check(rc, "srbd_mpc_backward")
+    if _only_x(seeds):
+        rc = L.srbd_mpc_backward(N, B, _ptrs(former_inputs), _ptrs(iterate), grad_x.data_ptr(), workspace.data_ptr(),
+                                 _ptrs(outs), st, _stream_ptr())
+        _native.check(rc, "srbd_mpc_backward")
+        return outs
+    sd, _ = _seed_struct(seeds, B, N, "mpc_backward", multi=False)
+    rc = L.srbd_mpc_backward_seeds(N, B, 1, _ptrs(former_inputs), _ptrs(iterate), ctypes.byref(sd),
+                                   workspace.data_ptr(), _ptrs(outs), st, _stream_ptr())
+    _native.check(rc, "srbd_mpc_backward_seeds")
     return outs
 
 
@@ -343,9 +414,15 @@ def _seed_block(grad_x: torch.Tensor, B: int, N: int, what: str):
                      f"got {tuple(grad_x.shape)}")
 
 
-def pdipm_backward_multi(qp: list, iterate: list[torch.Tensor], grad_x: torch.Tensor, N: int,
-                         status: torch.Tensor | None = None, outputs: list | None = None):
+def pdipm_backward_multi(qp: list, iterate: list[torch.Tensor], grad_x: torch.Tensor | None, N: int,
+                         status: torch.Tensor | None = None, outputs: list | None = None, *,
+                         grad_s: torch.Tensor | None = None, grad_z: torch.Tensor | None = None,
+                         grad_y: torch.Tensor | None = None, grad_objective: torch.Tensor | None = None):
     """``pdipm_backward`` for M seeds at one iterate with one factorisation and M solves.
+
+    ``grad_s``, ``grad_z``, ``grad_y``, ``grad_objective``: the cotangents of the solve's other outputs, as
+    ``pdipm_backward``; every given seed has the same M and the same sharing, (M, width) or (B, M, width)
+    with widths 24N, 16N, 16N, 14N and 1. ``grad_x`` may be None when another is given.
 
     ``grad_x`` of shape (M, 24N) is shared by every env (unit seeds: no (B, M, 24N) tensor is needed);
     (B, M, 24N) is per env. Returns [grad_H, grad_f, grad_A, grad_b, grad_G, grad_d], each (B, M, width);
@@ -359,12 +436,22 @@ def pdipm_backward_multi(qp: list, iterate: list[torch.Tensor], grad_x: torch.Te
     ins = list(qp) + list(iterate)
     _check_batch(ins, d.solver_in_nnz, B, "pdipm_backward_multi")
     _require_qp_and_iterate(ins, "pdipm_backward_multi")
-    M, stride = _seed_block(grad_x, B, N, "pdipm_backward_multi")
-    outs = _optional_outputs(outputs, d.former_out_nnz, B, grad_x.device, "pdipm_backward_multi outputs", M)
+    seeds = [grad_x, grad_s, grad_z, grad_y, grad_objective]
+    if _only_x(seeds):
+        M, stride = _seed_block(grad_x, B, N, "pdipm_backward_multi")
+    else:
+        sd, M = _seed_struct(seeds, B, N, "pdipm_backward_multi", multi=True)
+        if grad_objective is not None and ins[3] is None:
+            raise ValueError("pdipm_backward_multi: grad_objective needs f (qp[3])")
+    outs = _optional_outputs(outputs, d.former_out_nnz, B, iterate[0].device, "pdipm_backward_multi outputs", M)
     st = _check_status(status, B, "pdipm_backward_multi")
-    rc = _native.lib().srbd_pdipm_backward_multi(N, B, M, _ptrs(ins), grad_x.data_ptr(), stride, _ptrs(outs), st,
-                                                 _stream_ptr())
-    _native.check(rc, "srbd_pdipm_backward_multi")
+    if _only_x(seeds):
+        rc = _native.lib().srbd_pdipm_backward_multi(N, B, M, _ptrs(ins), grad_x.data_ptr(), stride, _ptrs(outs), st,
+                                                     _stream_ptr())
+        _native.check(rc, "srbd_pdipm_backward_multi")
+        return outs
+    rc = _native.lib().srbd_pdipm_backward_seeds(N, B, M, _ptrs(ins), ctypes.byref(sd), _ptrs(outs), st, _stream_ptr())
+    _native.check(rc, "srbd_pdipm_backward_seeds")
     return outs
 
 
@@ -401,9 +488,11 @@ def _input_mask(wrt) -> int:
     return mask
 
 
-def mpc_backward_multi(former_inputs: list[torch.Tensor], iterate: list[torch.Tensor], grad_x: torch.Tensor, N: int,
-                       wrt=None, status: torch.Tensor | None = None, outputs: list | None = None,
-                       workspace: torch.Tensor | None = None):
+def mpc_backward_multi(former_inputs: list[torch.Tensor], iterate: list[torch.Tensor], grad_x: torch.Tensor | None,
+                       N: int, wrt=None, status: torch.Tensor | None = None, outputs: list | None = None,
+                       workspace: torch.Tensor | None = None, *, grad_s: torch.Tensor | None = None,
+                       grad_z: torch.Tensor | None = None, grad_y: torch.Tensor | None = None,
+                       grad_objective: torch.Tensor | None = None):
     """``srbd_mpc_backward_multi``: qp_former (once per env) -> pdipm_backward_multi -> qp_former_backward_multi
     in one call (same bits), for the M seeds ``grad_x`` ((M, 24N) shared, or (B, M, 24N)).
 
@@ -411,55 +500,79 @@ def mpc_backward_multi(former_inputs: list[torch.Tensor], iterate: list[torch.Te
     gradients at those indices and None elsewhere: the others are neither computed nor allocated, and
     only the QP gradients the wanted inputs read are held in the workspace
     (``srbd_mpc_backward_multi_workspace_doubles``). ``outputs``: preallocated tensors instead (None
-    entries are skipped; ``wrt`` is then taken from it). The result is the derivative of the linearised
-    KKT conditions at the iterate: exact at convergence."""
+    entries are skipped; ``wrt`` is then taken from it). ``grad_s``, ``grad_z``, ``grad_y``,
+    ``grad_objective``: cotangents of the solve's other outputs, as ``pdipm_backward_multi``. The result is
+    the derivative of the linearised KKT conditions at the iterate: exact at convergence."""
     d = Dims(N)
     B = former_inputs[0].shape[0]
+    dev = former_inputs[0].device
     _check_batch(former_inputs, d.former_in_nnz, B, "mpc_backward_multi")
     _check_batch(list(iterate), d.solver_in_nnz[6:], B, "mpc_backward_multi iterate")
-    M, stride = _seed_block(grad_x, B, N, "mpc_backward_multi")
+    seeds = [grad_x, grad_s, grad_z, grad_y, grad_objective]
+    if _only_x(seeds):
+        M, stride = _seed_block(grad_x, B, N, "mpc_backward_multi")
+    else:
+        sd, M = _seed_struct(seeds, B, N, "mpc_backward_multi", multi=True)
     if outputs is not None:
         wrt = [i for i, t in enumerate(outputs) if t is not None]
     want = set(range(17)) if wrt is None else {int(i) for i in wrt}
     mask = _input_mask(want)
     if mask == 0:
         raise ValueError("mpc_backward_multi: no former input requested")
-    outs = _optional_outputs(outputs, d.former_in_nnz, B, grad_x.device, "mpc_backward_multi outputs", M, want)
+    outs = _optional_outputs(outputs, d.former_in_nnz, B, dev, "mpc_backward_multi outputs", M, want)
     L = _native.lib()
-    workspace = _workspace(workspace, L.srbd_mpc_backward_multi_workspace_doubles(N, B, M, mask), grad_x.device,
+    workspace = _workspace(workspace, L.srbd_mpc_backward_multi_workspace_doubles(N, B, M, mask), dev,
                            "mpc_backward_multi")
     st = _check_status(status, B, "mpc_backward_multi")
-    rc = L.srbd_mpc_backward_multi(N, B, M, _ptrs(former_inputs), _ptrs(iterate), grad_x.data_ptr(), stride,
+    if _only_x(seeds):
+        rc = L.srbd_mpc_backward_multi(N, B, M, _ptrs(former_inputs), _ptrs(iterate), grad_x.data_ptr(), stride,
+                                       workspace.data_ptr(), _ptrs(outs), st, _stream_ptr())
+        _native.check(rc, "srbd_mpc_backward_multi")
+        return outs
+    rc = L.srbd_mpc_backward_seeds(N, B, M, _ptrs(former_inputs), _ptrs(iterate), ctypes.byref(sd),
                                    workspace.data_ptr(), _ptrs(outs), st, _stream_ptr())
-    _native.check(rc, "srbd_mpc_backward_multi")
+    _native.check(rc, "srbd_mpc_backward_seeds")
     return outs
 
 
-def unit_seeds(N: int, rows, device="cuda") -> torch.Tensor:
-    """(len(rows), 24N) float64: the unit vectors of x at the indices ``rows`` (seeds shared by every env)."""
+def unit_seeds(N: int, rows, device="cuda", of: str = "x") -> torch.Tensor:
+    """(len(rows), width) float64: the unit vectors of the solve's output ``of`` (x: 24N, s and z: 16N, y: 14N)
+    at the indices ``rows`` (seeds shared by every env). ``of="objective"``: the (1, 1) seed 1.0, ``rows`` is
+    ignored."""
+    if of not in _native.SEED_KINDS:
+        raise ValueError(f"of: one of {', '.join(_native.SEED_KINDS)}, got {of!r}")
+    if of == "objective":
+        return torch.ones((1, 1), dtype=torch.float64, device=device)
+    w = _seed_widths(N)[_native.SEED_KINDS.index(of)]
     rows = [int(r) for r in rows]
-    if not rows or any(not 0 <= r < 24 * N for r in rows):
-        raise ValueError(f"rows: at least one index into x, each in 0..{24 * N - 1}")
-    g = torch.zeros((len(rows), 24 * N), dtype=torch.float64, device=device)
+    if not rows or any(not 0 <= r < w for r in rows):
+        raise ValueError(f"rows: at least one index into {of}, each in 0..{w - 1}")
+    g = torch.zeros((len(rows), w), dtype=torch.float64, device=device)
     g[torch.arange(len(rows), device=device), torch.tensor(rows, device=device)] = 1.0
     return g
 
 
 def mpc_jacobian(former_inputs: list[torch.Tensor], iterate: list[torch.Tensor], N: int, rows, wrt,
                  status: torch.Tensor | None = None, seeds: torch.Tensor | None = None,
-                 outputs: list | None = None, workspace: torch.Tensor | None = None):
+                 outputs: list | None = None, workspace: torch.Tensor | None = None, of: str = "x"):
     """Jacobians of solution components: for each former-input index in ``wrt``, (B, len(rows), width) =
     d x[rows] / d input (a list of 17, None elsewhere). ``rows`` are indices into x (24N: the states
     x_1..x_N, then the inputs u_0..u_{N-1}). One factorisation per env and len(rows) solves, with unit
     seeds shared by every env (``seeds``: ``unit_seeds(N, rows)`` kept by the caller, e.g. for graph
-    capture). The Jacobian is that of the linearised KKT conditions at the iterate: exact
-    at convergence."""
+    capture). ``of``: the output differentiated, one of x, s, z, y, objective -- ``rows`` index into it
+    (s and z: 16N, y: 14N); ``of="objective"`` ignores ``rows`` and returns (B, 1, width), the gradient of the
+    MPC cost. The Jacobian is that of the linearised KKT conditions at the iterate: exact at
+    convergence."""
+    if of not in _native.SEED_KINDS:
+        raise ValueError(f"mpc_jacobian: of must be one of {', '.join(_native.SEED_KINDS)}, got {of!r}")
+    n_rows = 1 if of == "objective" else len(list(rows))
     if seeds is None:
-        seeds = unit_seeds(N, rows, former_inputs[0].device)
-    elif seeds.dim() != 2 or seeds.shape[0] != len(list(rows)):
-        raise ValueError("mpc_jacobian: seeds must be unit_seeds(N, rows)")
-    return mpc_backward_multi(former_inputs, iterate, seeds, N, wrt=wrt, status=status, outputs=outputs,
-                              workspace=workspace)
+        seeds = unit_seeds(N, rows, former_inputs[0].device, of)
+    elif seeds.dim() != 2 or seeds.shape[0] != n_rows:
+        raise ValueError("mpc_jacobian: seeds must be unit_seeds(N, rows, of=of)")
+    kw = {} if of == "x" else {"grad_" + of: seeds}
+    return mpc_backward_multi(former_inputs, iterate, seeds if of == "x" else None, N, wrt=wrt, status=status,
+                              outputs=outputs, workspace=workspace, **kw)
 
 
 def mpc_feedback_gain(former_inputs: list[torch.Tensor], iterate: list[torch.Tensor], N: int,
@@ -504,14 +617,59 @@ class _MPCSolveFunction(torch.autograd.Function):
         return (None, None, None) + tuple(o.view(s) if o is not None else None for o, s in zip(outs, ctx.shapes))
 
 
-def mpc_solve_autograd(former_inputs: list[torch.Tensor], N: int, n_iter: int, y0: float = 1.0) -> torch.Tensor:
+class _MPCSolveOutputsFunction(torch.autograd.Function):
+    """The named outputs of mpc_solve(former_inputs), among x, s, z, y and the objective: forward ``srbd_mpc_solve_fused`` (``_info`` for the objective),
+    backward ``srbd_mpc_backward`` / ``srbd_mpc_backward_seeds`` on the saved iterate (the adjoint KKT solve and
+    the former's vector-Jacobian product) with whichever cotangents autograd supplies."""
+
+    @staticmethod
+    def forward(ctx, N, n_iter, y0, outputs, *former_inputs):
+        ins = [t.detach().contiguous() for t in former_inputs]
+        B = ins[0].shape[0]
+        J = torch.empty(B, dtype=torch.float64, device=ins[0].device) if "objective" in outputs else None
+        x, s, z, y = mpc_solve(ins, N, n_iter, y0, objective=J)[:4]
+        ctx.N = N
+        ctx.outputs = outputs
+        ctx.shapes = [t.shape for t in former_inputs]
+        ctx.save_for_backward(*ins, x, s, z, y)
+        ctx.set_materialize_grads(False)  # an unused output's cotangent stays None: a NULL seed
+        res = {"x": x, "s": s, "z": z, "y": y}
+        # copies: the saved iterate stays what the backward pass linearises at
+        return tuple(J if k == "objective" else res[k].clone() for k in outputs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        saved = ctx.saved_tensors
+        ins, iterate = list(saved[:17]), list(saved[17:])
+        d = Dims(ctx.N)
+        B = ins[0].shape[0]
+        need = ctx.needs_input_grad[4:]
+        seeds = {"grad_" + k: (None if g is None else g.contiguous()) for k, g in zip(ctx.outputs, grads)}
+        if all(g is None for g in seeds.values()):
+            return (None,) * (4 + len(ins))
+        outs = [torch.empty((B, w), dtype=torch.float64, device=ins[0].device) if n else None
+                for w, n in zip(d.former_in_nnz, need)]
+        mpc_backward(ins, iterate, seeds.pop("grad_x", None), ctx.N, outputs=outs, **seeds)
+        return (None, None, None, None) + tuple(o.view(s) if o is not None else None
+                                                for o, s in zip(outs, ctx.shapes))
+
+
+def mpc_solve_autograd(former_inputs: list[torch.Tensor], N: int, n_iter: int, y0: float = 1.0,
+                       outputs=("x",)):
     """The differentiable MPC QP layer: ``x`` (B, 24N) of ``mpc_solve`` (qp_former + cold-started PDIPM,
     one fused kernel) as a ``torch.autograd.Function``. ``torch.autograd.grad(loss(x), inp)`` works for
     every former input that requires grad (x and u, the linearisation point, get zeros; inputs without
-    ``requires_grad`` get None). The gradient is that of the linearised KKT conditions at the returned
+    ``requires_grad`` get None). ``outputs``: the default returns x alone; any other choice returns a tuple
+    of the named outputs among x, s, z, y and objective (J = 0.5 x^T H x + f^T x, the MPC cost, (B,)), and
+    a loss may use any of them. The gradient is that of the linearised KKT conditions at the returned
     iterate: exact at convergence, and within 0.1-1 % of finite differences of the solve at 35
     iterations (DESIGN.md)."""
-    return _MPCSolveFunction.apply(N, n_iter, float(y0), *former_inputs)
+    outputs = tuple(outputs)
+    if not outputs or len(set(outputs)) != len(outputs) or any(k not in _native.SEED_KINDS for k in outputs):
+        raise ValueError(f"mpc_solve_autograd: outputs must be distinct names out of {', '.join(_native.SEED_KINDS)}")
+    if outputs == ("x",):
+        return _MPCSolveFunction.apply(N, n_iter, float(y0), *former_inputs)
+    return _MPCSolveOutputsFunction.apply(N, n_iter, float(y0), outputs, *former_inputs)
 
 
 # ---- backward pass of the controller step's FP32 ends (include/srbd_mpc.h: wrench cotangent -> FP32 inputs) ----
@@ -602,23 +760,38 @@ def prepare_inputs_backward(prep, input_grads: list, N: int, B: int, wrt, grad_w
 
 
 def mpc_step_backward(prep, former_inputs: list[torch.Tensor], iterate: list[torch.Tensor],
-                      grad_wrench: torch.Tensor, N: int, wrt, grad_tau: torch.Tensor | None = None,
+                      grad_wrench: torch.Tensor | None, N: int, wrt, grad_tau: torch.Tensor | None = None,
                       contact_jacobian: torch.Tensor | None = None, contact_bool: torch.Tensor | None = None,
                       grad_wpd_out: torch.Tensor | None = None, grad_yaw_out: torch.Tensor | None = None,
-                      status: torch.Tensor | None = None, workspace: torch.Tensor | None = None) -> dict:
+                      status: torch.Tensor | None = None, workspace: torch.Tensor | None = None,
+                      grad_cost: torch.Tensor | None = None) -> dict:
     """``srbd_mpc_step_backward``: wrench VJP -> adjoint KKT solve and former VJP -> input-preparation VJP in one
     call (the bits of the three calls), from what a controller step with ``keep_solution`` wrote. Only the
-    former-input cotangents the fields in ``wrt`` read are computed. Returns a dict of float32 gradients."""
-    import ctypes
+    former-input cotangents the fields in ``wrt`` read are computed. ``grad_cost`` (B,) float32: the cotangent
+    of the step's MPC cost (``srbd_mpc_step_backward_cost``); ``grad_wrench`` may then be None. Returns a dict
+    of float32 gradients."""
     what = "mpc_step_backward"
     d = Dims(N)
     B = former_inputs[0].shape[0]
+    dev = former_inputs[0].device
     _check_batch(former_inputs, d.former_in_nnz, B, what)
     _check_batch(list(iterate), d.solver_in_nnz[6:], B, what + " iterate")
-    out, ptrs, mask = _prep_grad_outputs(B, N, wrt, grad_wrench.device, what)
+    if grad_wrench is None and grad_cost is None:
+        raise ValueError(f"{what}: grad_wrench and grad_cost are both None")
+    out, ptrs, mask = _prep_grad_outputs(B, N, wrt, dev, what)
     L = _native.lib()
-    workspace = _workspace(workspace, L.srbd_mpc_step_backward_workspace_doubles(N, B, mask), grad_wrench.device, what)
     ndof, J, cb, gt = _torque_cotangent(B, grad_tau, contact_jacobian, contact_bool, what)
+    if grad_cost is not None:
+        workspace = _workspace(workspace, L.srbd_mpc_step_backward_cost_workspace_doubles(N, B, mask), dev, what)
+        rc = L.srbd_mpc_step_backward_cost(
+            N, B, ctypes.byref(prep), _ptrs(former_inputs), _ptrs(iterate),
+            _f32_arg(grad_wrench, (B, 2, 6), what, "grad_wrench"), _f32_arg(grad_cost, (B,), what, "grad_cost"),
+            ndof, J, cb, gt, _f32_arg(grad_wpd_out, (B, 3), what, "grad_wpd_out"),
+            _f32_arg(grad_yaw_out, (B,), what, "grad_yaw_out"), workspace.data_ptr(), ptrs,
+            _check_status(status, B, what), _stream_ptr())
+        _native.check(rc, "srbd_mpc_step_backward_cost")
+        return out
+    workspace = _workspace(workspace, L.srbd_mpc_step_backward_workspace_doubles(N, B, mask), dev, what)
     rc = L.srbd_mpc_step_backward(
         N, B, ctypes.byref(prep), _ptrs(former_inputs), _ptrs(iterate),
         _f32_arg(grad_wrench, (B, 2, 6), what, "grad_wrench"), ndof, J, cb, gt,

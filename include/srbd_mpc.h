@@ -321,14 +321,15 @@ int srbd_u0_wrench_torque(int horizon, int batch, const double* x, const float* 
 int srbd_dense_scatter(int batch, int nnz, int rc, const int* inverse_index, const double* values,
                        double* dense, void* stream);
 
-/* ---- Backward pass: gradients of a loss L(x) through the QP solve and the former --------------------
+/* ---- Backward pass: gradients of a loss on a solve's outputs through the QP solve and the former -----
  * The iterate (x, s, z, y) a solve returned is read as a root of the solver's regularised KKT
  * conditions; their Newton matrix K is symmetric, so one solve of
  *   K [lx; ls; lz; ly] = [grad_x; 0; 0; 0]
  * (one factorisation, one solve, one refinement step, the forward LDS-resident kernel's phases) gives
  * every gradient. At a non-converged iterate this is the exact derivative of the linearised KKT
- * conditions at that iterate (qpth's convention). Only a seed on x is taken: seeds on s, z and y are
- * out of scope. All entry points: host arrays of device pointers, asynchronous on `stream`, no device
+ * conditions at that iterate (qpth's convention). The entries named *_seeds below take cotangents of
+ * every output of a solve -- x, s, z, y and the objective -- as the right-hand side of the same K; the
+ * others take grad_x alone and are those entries with one cotangent. All entry points: host arrays of device pointers, asynchronous on `stream`, no device
  * allocation (capture-safe after srbd_prepare_device), batch == 0 and bad arguments return without
  * touching the GPU, errors through srbd_last_error().
  *
@@ -338,7 +339,7 @@ int srbd_dense_scatter(int batch, int nnz, int rc, const int* inverse_index, con
 #define SRBD_STATUS_UNSUPPORTED 8
 
 /* inputs: srbd_pdipm's ten, in its order (Q_val, G_val, A_val, f, h, b, x, s, z, y); f, h, b are not
- * read and may be NULL. grad_x (B, 24N) = dL/dx. qp_grads: six outputs in qp_former's output order and
+ * read here and may be NULL. grad_x (B, 24N) = dL/dx. qp_grads: six outputs in qp_former's output order and
  * CCS widths, each skipped when NULL (asking for a subset changes no bit of the others):
  *   grad_H (24N)       -lx[c] x[c]                      grad_f (24N)  -lx
  *   grad_A (122N-24)   -(lx[c] y[r] + ly[r] x[c])       grad_b (14N)   ly
@@ -408,6 +409,37 @@ size_t srbd_mpc_backward_multi_workspace_doubles(int horizon, int batch, int n_s
 int srbd_mpc_backward_multi(int horizon, int batch, int n_seeds, const double* const* former_inputs,
                             const double* const* iterate, const double* grad_x, size_t grad_x_env_stride,
                             double* workspace, double* const* input_grads, int* status, void* stream);
+
+/* ---- Seeds on every output of a solve: x, s, z, y and the objective -----------------------------------
+ * A solve returns x, the slacks s = d - G x (the friction-cone and force-limit margins), the multipliers z
+ * and y, and on request the objective J = 1/2 x^T H x + f^T x (the MPC cost). With cotangents g_x, g_s,
+ * g_z, g_y, g_J of a loss, the adjoint is the solution of the same symmetric K with the full right-hand side
+ *   K [lx; ls; lz; ly] = [g_x + g_J (H o x + f); g_s; g_z; g_y],
+ * the six gradient formulas of srbd_pdipm_backward hold unchanged (ls enters none of them), and J's explicit
+ * dependence on the data adds g_J (1/2 x[c] x[c]) to grad_H[c] and g_J x[c] to grad_f[c] (when those are
+ * written). One factorisation, and per seed one solve and one refinement step, as above. A NULL cotangent is
+ * zero: with grad_x alone an entry gives the bits of its x-only counterpart, and a NULL array gives what an
+ * all-zero one gives. All five NULL is a bad argument. f (solver input 3) is read only with grad_objective
+ * and is required then.
+ *
+ * Each given array holds one row per seed, of its width: row e * n_seeds + k for seed k of env e (B * M
+ * rows), or with `shared` row k for every env (M rows; unit seeds of a Jacobian). n_seeds = 1, shared = 0 is
+ * one seed per env. Outputs, status words and conventions as srbd_pdipm_backward_multi. */
+typedef struct srbd_backward_seeds {
+  const double *grad_x, *grad_s, *grad_z, *grad_y; /* widths 24N, 16N, 16N, 14N; NULL = zero */
+  const double* grad_objective;                    /* width 1; NULL = zero */
+  int shared; /* 0: each array holds B*M rows, row e*M+k; 1: M rows shared by every env */
+} srbd_backward_seeds;
+
+int srbd_pdipm_backward_seeds(int horizon, int batch, int n_seeds, const double* const* inputs,
+                              const srbd_backward_seeds* seeds, double* const* qp_grads, int* status,
+                              void* stream);
+/* srbd_qp_former -> srbd_pdipm_backward_seeds -> srbd_qp_former_backward_multi in one call (same bits); the
+ * former's QP in the workspace supplies f. workspace: srbd_mpc_backward_multi_workspace_doubles doubles. All
+ * 17 input_grads may be NULL: only `status` is written then. */
+int srbd_mpc_backward_seeds(int horizon, int batch, int n_seeds, const double* const* former_inputs,
+                            const double* const* iterate, const srbd_backward_seeds* seeds, double* workspace,
+                            double* const* input_grads, int* status, void* stream);
 
 /* ---- Backward pass of the controller step: wrench cotangent -> the controller's FP32 tensors ---------
  * srbd_mpc_step maps the FP32 tensors of srbd_mpc_prep to the FP32 foot wrench (and stance torque). The
@@ -490,6 +522,19 @@ int srbd_mpc_step_backward(int horizon, int batch, const srbd_mpc_prep* prep, co
                            const float* contact_jacobian, const float* contact_bool, const float* grad_tau,
                            const float* grad_wpd_out, const float* grad_yaw_out, double* workspace,
                            float* const* prep_grads, int* status, void* stream);
+
+/* srbd_mpc_step_backward with the cotangent of the step's MPC cost: grad_cost (B) float32 is the cotangent
+ * of objective_f32 (srbd_mpc_step_info). It is widened to FP64 and enters the adjoint as grad_objective; the
+ * one rounding of J to float32 is read as the identity. grad_wrench may be NULL when grad_cost is not (and
+ * grad_tau must then be NULL); with grad_cost NULL this is srbd_mpc_step_backward. The workspace is that
+ * entry's, laid out alike, plus the widened cotangent (B doubles) behind it. */
+size_t srbd_mpc_step_backward_cost_workspace_doubles(int horizon, int batch, unsigned prep_mask /* 0 = all 15 */);
+int srbd_mpc_step_backward_cost(int horizon, int batch, const srbd_mpc_prep* prep,
+                                const double* const* former_inputs, const double* const* iterate /* x, s, z, y */,
+                                const float* grad_wrench, const float* grad_cost, int ndof,
+                                const float* contact_jacobian, const float* contact_bool, const float* grad_tau,
+                                const float* grad_wpd_out, const float* grad_yaw_out, double* workspace,
+                                float* const* prep_grads, int* status, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,468 @@
+"""Seeds on every output of a solve -- x, s, z, y and the objective (the MPC cost) -- on the GPU:
+srbd_pdipm_backward_seeds, srbd_mpc_backward_seeds, srbd_mpc_step_backward_cost and the Python surface over
+them (the grad_s / grad_z / grad_y / grad_objective keywords, mpc_jacobian(of=...), mpc_solve_autograd(outputs=...),
+MPCControllerHIP.backward(grad_cost=...), run_autograd(return_cost=True)).
+
+Most criteria need no tolerance: the x-only entries keep their bits (1), a seed row has the bits of the call on
+that row alone (2), a NULL cotangent is an all-zero one (3), the composed entries are their parts (4, 8).
+Accuracy (5) is measured against the dense refined adjoint with the full right-hand side
+(tests/_backward_full_ref.py), norm-wise per env and per output, no env excluded, with the CASES tolerance of the
+K that produced the iterate; tests/test_backward_full_ref.py shows on the same inputs that the plain-FP64
+restatement of the kernel's elimination stays inside those tolerances. Inputs: tests/_backward_cases.py (B = 16,
+iterates from oracle.pdipm).
+"""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from biped_pympc_amd import _native, layout, solver
+from tests import _backward_cases as C
+from tests import _backward_full_ref as fr
+from tests._util import rel_err_rows
+
+pytestmark = pytest.mark.gpu
+
+FIELDS = ("x", "s", "z", "y", "objective")
+
+
+def _cuda(arrs):
+    return [torch.from_numpy(np.ascontiguousarray(a)).cuda() if a is not None else None for a in arrs]
+
+
+def _np(t):
+    return t.cpu().numpy()
+
+
+@functools.lru_cache(maxsize=None)
+def _dev_case(N, gait, K):
+    """(former inputs, QP in the solver's order, iterate) on the device."""
+    ins, qp = C.workload(N, gait)
+    return _cuda(ins), _cuda(qp), _cuda(C.iterate(N, gait, K))
+
+
+@functools.lru_cache(maxsize=None)
+def _dev_seeds(N):
+    """field -> (B, width) cotangent on the device (objective: (B,))."""
+    a = fr.seed_arrays(N)
+    return {k: torch.from_numpy(np.ascontiguousarray(a[k])).cuda() for k in FIELDS}
+
+
+def _kw(N, kind):
+    """The keywords of solver.pdipm_backward / mpc_backward for one seed kind: (grad_x, {grad_*: tensor})."""
+    sd = _dev_seeds(N)
+    if kind == "all":
+        return sd["x"], {"grad_" + k: sd[k] for k in FIELDS[1:]}
+    if kind == "x":
+        return sd["x"], {}
+    return None, {"grad_" + kind: sd[kind]}
+
+
+def _status(B=C.BATCH):
+    return torch.full((B,), -1, dtype=torch.int32, device="cuda")
+
+
+def _seeds_entry(qp, it, N, M, shared, seeds: dict, status=None):
+    """srbd_pdipm_backward_seeds itself: seeds field -> tensor of B * M (or M) rows."""
+    fn = _native.lib().srbd_pdipm_backward_seeds
+    B = it[0].shape[0]
+    sd = _native.BackwardSeeds(*[seeds[k].data_ptr() if seeds.get(k) is not None else None for k in FIELDS],
+                               1 if shared else 0)
+    outs = [torch.full((B, M, w), float("nan"), dtype=torch.float64, device="cuda")
+            for w in layout.Dims(N).former_out_nnz]
+    rc = fn(N, B, M, solver._ptrs(list(qp) + list(it)), ctypes.byref(sd), solver._ptrs(outs),
+            None if status is None else status.data_ptr(), solver._stream_ptr())
+    _native.check(rc, "srbd_pdipm_backward_seeds")
+    return outs
+
+
+# ---- 1. the x-only entries keep their bits --------------------------------------------------------
+
+@pytest.mark.parametrize("N", C.HORIZONS)
+def test_x_only_entries_equal_the_seeds_entry_with_grad_x_alone(N):
+    _, qp, it = _dev_case(N, "random", 5)
+    g = _dev_seeds(N)["x"]
+    st_old, st_new = _status(), _status()
+    old = solver.pdipm_backward(qp, it, g, N, status=st_old)
+    new = _seeds_entry(qp, it, N, 1, False, {"x": g}, st_new)
+    block = torch.stack([g, g.flip(0), g], dim=1).contiguous()  # M = 3, per env
+    old_m = solver.pdipm_backward_multi(qp, it, block, N)
+    new_m = _seeds_entry(qp, it, N, 3, False, {"x": block})
+    shared = g[:2].contiguous()  # M = 2, shared by every env
+    old_s = solver.pdipm_backward_multi(qp, it, shared, N)
+    new_s = _seeds_entry(qp, it, N, 2, True, {"x": shared})
+    # grad_x alone runs the kernels' x-only instantiation; all-zero tensors for the rest run the full one
+    sd = _dev_seeds(N)
+    zeros = {k: torch.zeros_like(sd[k]) for k in FIELDS[1:]}
+    full = _seeds_entry(qp, it, N, 1, False, dict(zeros, x=g))
+    zeros_m = {k: torch.zeros((C.BATCH, 3, v.numel() // C.BATCH), dtype=torch.float64, device="cuda")
+               for k, v in zeros.items()}
+    full_m = _seeds_entry(qp, it, N, 3, False, dict(zeros_m, x=block))
+    torch.cuda.synchronize()
+    assert torch.all(st_old == 0) and torch.equal(st_old, st_new)
+    for o, name in enumerate(C.NAMES):
+        assert torch.equal(new[o][:, 0], old[o]), name
+        assert torch.equal(new_m[o], old_m[o]) and torch.equal(new_s[o], old_s[o]), name
+        assert torch.equal(full[o][:, 0], old[o]) and torch.equal(full_m[o], old_m[o]), name
+        assert torch.isfinite(old[o]).all(), name
+
+
+# ---- 2. a seed row has the bits of the call on that row alone -------------------------------------
+
+def _mixed_rows(N):
+    """M = 3 rows of mixed kinds: `all`, z only, `all` again -- and objective only in place of row 1 for the
+    second block. Fields a row does not give are zero rows of the block."""
+    sd = _dev_seeds(N)
+    zero = {k: torch.zeros_like(sd[k]) for k in FIELDS}
+    rows_a = [dict(sd), {"z": sd["z"]}, dict(sd)]
+    rows_b = [dict(sd), {"objective": sd["objective"]}, dict(sd)]
+
+    def block(rows):
+        return {k: torch.stack([r.get(k, zero[k]) for r in rows], dim=1).contiguous().view(C.BATCH, 3, -1)
+                for k in FIELDS}
+    return (rows_a, block(rows_a)), (rows_b, block(rows_b))
+
+
+@pytest.mark.parametrize("N", [3, 10])
+def test_each_mixed_seed_row_has_the_bits_of_the_single_seed_call(N):
+    _, qp, it = _dev_case(N, "random", 5)
+    for rows, block in _mixed_rows(N):
+        st = _status()
+        got = solver.pdipm_backward_multi(qp, it, block["x"], N, status=st,
+                                          **{"grad_" + k: block[k] for k in FIELDS[1:]})
+        torch.cuda.synchronize()
+        assert torch.all(st == 0), st
+        for k, row in enumerate(rows):
+            single = solver.pdipm_backward(qp, it, row.get("x"), N, **{"grad_" + f: row[f] for f in FIELDS[1:] if f in row})
+            for o, name in enumerate(C.NAMES):
+                assert torch.equal(got[o][:, k], single[o]), (name, k)
+        for o, name in enumerate(C.NAMES):
+            assert torch.equal(got[o][:, 2], got[o][:, 0]), name  # no state leaks from row 1 into row 2
+            assert not torch.equal(got[o][:, 1], got[o][:, 0]), name
+
+
+@pytest.mark.parametrize("N", [3, 10])
+def test_shared_seed_rows_equal_materialised_ones(N):
+    _, qp, it = _dev_case(N, "random", 5)
+    sd = _dev_seeds(N)
+    shared = {k: sd[k][:3].contiguous().view(3, -1) for k in FIELDS}  # (M, w): envs 0..2's rows as the seeds
+    full = {k: v[None].expand(C.BATCH, -1, -1).contiguous() for k, v in shared.items()}
+    a = solver.pdipm_backward_multi(qp, it, shared["x"], N, **{"grad_" + k: shared[k] for k in FIELDS[1:]})
+    b = solver.pdipm_backward_multi(qp, it, full["x"], N, **{"grad_" + k: full[k] for k in FIELDS[1:]})
+    torch.cuda.synchronize()
+    for o, name in enumerate(C.NAMES):
+        assert torch.equal(a[o], b[o]), name
+    with pytest.raises(ValueError, match="same M and the same sharing"):
+        solver.pdipm_backward_multi(qp, it, shared["x"], N, grad_s=full["s"])
+
+
+# ---- 3. a NULL cotangent is an all-zero one -------------------------------------------------------
+
+@pytest.mark.parametrize("null", ["s", "z", "y", "objective", "x"])
+def test_a_null_cotangent_equals_an_all_zero_tensor(null):
+    N = 3
+    _, qp, it = _dev_case(N, "random", 5)
+    sd = dict(_dev_seeds(N))
+    zeroed = dict(sd, **{null: torch.zeros_like(sd[null])})
+    nulled = dict(sd, **{null: None})
+    a = solver.pdipm_backward(qp, it, zeroed["x"], N, **{"grad_" + k: zeroed[k] for k in FIELDS[1:]})
+    b = solver.pdipm_backward(qp, it, nulled["x"], N, **{"grad_" + k: nulled[k] for k in FIELDS[1:]})
+    torch.cuda.synchronize()
+    for o, name in enumerate(C.NAMES):
+        assert torch.equal(a[o], b[o]), name
+        assert torch.isfinite(a[o]).all(), name
+
+
+# ---- 4. composition -------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("N", [3, 10])
+def test_mpc_backward_with_seeds_equals_the_three_calls_and_wrt_changes_no_bit(N):
+    ins, _, it = _dev_case(N, "random", 5)
+    sd = _dev_seeds(N)
+    kw = {"grad_s": sd["s"], "grad_objective": sd["objective"]}
+    qp = solver.qp_former(ins, N)  # H, f, A, b, G, d
+    grads = solver.pdipm_backward([qp[0], qp[4], qp[2], qp[1], qp[5], qp[3]], it, None, N, **kw)
+    chain = solver.qp_former_backward(ins, grads, N)
+    st = _status()
+    full = solver.mpc_backward(ins, it, None, N, status=st, **kw)
+    torch.cuda.synchronize()
+    assert torch.all(st == 0)
+    for i, name in enumerate(layout.FORMER_IN_NAMES):
+        assert torch.equal(full[i], chain[i]), name
+    # subsets: x0 reads grad_b only (grad_H and grad_f, where the objective's direct terms land, are not
+    # materialised); Q reads grad_H and grad_f; dt and a residual read grad_A and grad_b
+    for wrt in ([0], [13], [3, 13, 16], [4, 15]):
+        outs = [torch.full_like(full[i], float("nan")) if i in wrt else None for i in range(17)]
+        part = solver.mpc_backward(ins, it, None, N, outputs=outs, **kw)
+        multi = solver.mpc_backward_multi(ins, it, None, N, wrt=wrt, grad_s=sd["s"][:, None, :].contiguous(),
+                                          grad_objective=sd["objective"][:, None, None].contiguous())
+        torch.cuda.synchronize()
+        for i in range(17):
+            if i in wrt:
+                assert torch.equal(part[i], full[i]) and torch.equal(multi[i][:, 0], full[i]), layout.FORMER_IN_NAMES[i]
+            else:
+                assert part[i] is None and multi[i] is None
+    # the direct terms reach Q: without them its gradient differs
+    no_direct = solver.qp_former_backward(ins, [solver.pdipm_backward(
+        [qp[0], qp[4], qp[2], qp[1], qp[5], qp[3]], it, None, N, grad_s=sd["s"])[k] for k in range(6)], N)
+    assert not torch.equal(no_direct[13], full[13])
+
+
+# ---- 5. accuracy ----------------------------------------------------------------------------------
+
+ACCURACY = [(N, 5) for N in C.HORIZONS] + [(10, K) for K in (1, 10, 20)]
+
+
+@pytest.mark.parametrize("gait", C.GAITS)
+@pytest.mark.parametrize("N,K", ACCURACY)
+def test_every_seed_kind_matches_the_dense_adjoint(N, K, gait):
+    """Measured on an MI355X, worst over the sixteen cases, five kinds, envs and outputs: 5.1e-14 (N = 10, K = 5,
+    all five seeds; the tightest tolerance is 1e-10). The table per (N, K, kind) is in DESIGN.md 6c."""
+    tol = dict(C.CASES)[K]
+    _, qp, it = _dev_case(N, gait, K)
+    ref = fr.reference(N, gait, K)
+    worst = {}
+    for kind in fr.KINDS:
+        gx, kw = _kw(N, kind)
+        st = _status()
+        got = solver.pdipm_backward(qp, it, gx, N, status=st, **kw)
+        torch.cuda.synchronize()
+        assert torch.all(st == 0), (kind, st)
+        errs = np.stack([rel_err_rows(_np(got[o]), ref[kind][o]) for o in range(6)])
+        o, e = np.unravel_index(errs.argmax(), errs.shape)
+        worst[kind] = float(errs.max())
+        print(f"N={N} K={K} {gait} seed {kind}: max rel err {errs.max():.3e} ({C.NAMES[o]}, env {e}), tol {tol:.0e}")
+    for kind, w in worst.items():
+        assert w <= tol, (kind, w)
+
+
+# ---- 6. behaviour ---------------------------------------------------------------------------------
+
+def test_unsupported_qp_gets_nan_and_status_8_neighbours_unchanged():
+    N, bad = 3, 5
+    _, qp, it = _dev_case(N, "random", 5)
+    (rows, block), _ = _mixed_rows(N)
+    kw = {"grad_" + k: block[k] for k in FIELDS[1:]}
+    base = solver.pdipm_backward_multi(qp, it, block["x"], N, **kw)
+    H = qp[0].clone()
+    H[bad, 12:24] *= 1.5  # stage 1 of the x weights: no longer stage-invariant
+    st = _status()
+    got = solver.pdipm_backward_multi([H] + qp[1:], it, block["x"], N, status=st, **kw)
+    st1 = _status()
+    one = solver.pdipm_backward([H] + qp[1:], it, None, N, status=st1, grad_z=_dev_seeds(N)["z"])
+    torch.cuda.synchronize()
+    want = torch.zeros(C.BATCH, dtype=torch.int32, device="cuda")
+    want[bad] = _native.STATUS_UNSUPPORTED
+    assert torch.equal(st, want) and torch.equal(st1, want), (st, st1)
+    others = [e for e in range(C.BATCH) if e != bad]
+    for o, name in enumerate(C.NAMES):
+        assert torch.isnan(got[o][bad]).all() and torch.isnan(one[o][bad]).all(), name
+        assert torch.equal(got[o][others], base[o][others]), name
+        assert torch.equal(one[o][others], base[o][others, 1]), name  # row 1 is the z seed alone
+
+
+def test_rows_do_not_depend_on_batch_size_position_or_stream():
+    N, K = 10, 10
+    _, qp, it = _dev_case(N, "random", K)
+    (rows, block), _ = _mixed_rows(N)
+    sd = _dev_seeds(N)
+    multi = lambda q, i, b: solver.pdipm_backward_multi(q, i, b["x"], N, **{"grad_" + k: b[k] for k in FIELDS[1:]})  # noqa: E731
+    single = lambda q, i, s: solver.pdipm_backward(q, i, s["x"], N, **{"grad_" + k: s[k] for k in FIELDS[1:]})  # noqa: E731
+    base, base1 = multi(qp, it, block), single(qp, it, sd)
+    idx = torch.arange(67, device="cuda") % C.BATCH
+    idx[66] = 0  # env 0 at position 0 and at position 66 of 67
+    g = lambda t: t[idx].contiguous()  # noqa: E731
+    big = multi([g(t) for t in qp], [g(t) for t in it], {k: g(v) for k, v in block.items()})
+    big1 = single([g(t) for t in qp], [g(t) for t in it], {k: g(v) for k, v in sd.items()})
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(s1):
+        a = multi(qp, it, block)
+    with torch.cuda.stream(s2):
+        b = single(qp, it, sd)
+    torch.cuda.synchronize()
+    for o, name in enumerate(C.NAMES):
+        assert torch.equal(big[o], base[o][idx]) and torch.equal(big1[o], base1[o][idx]), name
+        assert torch.equal(big[o][66], base[o][0]) and torch.equal(big1[o][66], base1[o][0]), name
+        assert torch.equal(a[o], base[o]) and torch.equal(b[o], base1[o]), name
+
+
+def test_grad_objective_without_f_raises():
+    N = 3
+    _, qp, it = _dev_case(N, "random", 5)
+    gJ = _dev_seeds(N)["objective"]
+    no_f = [qp[0], qp[1], qp[2], None, None, None]
+    with pytest.raises(ValueError, match="needs f"):
+        solver.pdipm_backward(no_f, it, None, N, grad_objective=gJ)
+    with pytest.raises(RuntimeError, match="grad_objective needs f"):  # the C entry's own check
+        _seeds_entry(no_f, it, N, 1, False, {"objective": gJ})
+    with pytest.raises(ValueError, match="no seed given"):
+        solver.pdipm_backward(qp, it, None, N)
+    got = solver.pdipm_backward(no_f, it, None, N, grad_s=_dev_seeds(N)["s"])  # f is not read without it
+    want = solver.pdipm_backward(qp, it, None, N, grad_s=_dev_seeds(N)["s"])
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(got, want))
+
+
+# ---- 7. the Python surface ------------------------------------------------------------------------
+
+@pytest.mark.parametrize("N", [3, 10])
+def test_autograd_over_s_and_the_objective_equals_the_explicit_call(N):
+    K = 5
+    ins, _, _ = _dev_case(N, "random", K)
+    wrt = [15, 4, 13]  # residual_lin_accel, dt, Q
+    leaves = [t.clone().requires_grad_(i in wrt) for i, t in enumerate(ins)]
+    x, s, J = solver.mpc_solve_autograd(leaves, N, K, outputs=("x", "s", "objective"))
+    Jd = torch.empty(C.BATCH, dtype=torch.float64, device="cuda")
+    sol = [t.clone() for t in solver.mpc_solve(ins, N, K, objective=Jd)[:4]]
+    assert torch.equal(x.detach(), sol[0]) and torch.equal(s.detach(), sol[1]) and torch.equal(J.detach(), Jd)
+    got = torch.autograd.grad(s.min(dim=1).values.sum() + J.sum(), [leaves[i] for i in wrt])
+    sl = sol[1].clone().requires_grad_(True)
+    (gs,) = torch.autograd.grad(sl.min(dim=1).values.sum(), [sl])
+    outs = [torch.empty_like(t) if i in wrt else None for i, t in enumerate(ins)]
+    want = solver.mpc_backward(ins, sol, None, N, outputs=outs, grad_s=gs.contiguous(),
+                               grad_objective=torch.ones_like(Jd))
+    torch.cuda.synchronize()
+    for g, i in zip(got, wrt):
+        assert g.shape == ins[i].shape and torch.equal(g, want[i]), layout.FORMER_IN_NAMES[i]
+        assert torch.isfinite(g).all() and g.abs().max() > 0, layout.FORMER_IN_NAMES[i]
+    x_only = solver.mpc_solve_autograd(leaves, N, K)  # the default: x alone, a tensor
+    assert isinstance(x_only, torch.Tensor) and torch.equal(x_only.detach(), sol[0])
+    (gx,) = torch.autograd.grad(x_only.square().sum(), [leaves[15]])
+    assert torch.equal(gx, solver.mpc_backward(ins, sol, (2.0 * sol[0]).contiguous(), N)[15])
+
+
+def test_jacobian_of_s_and_of_the_objective_are_the_unit_seed_rows():
+    N = 3
+    ins, _, it = _dev_case(N, "random", 5)
+    rows = [0, 7, 16 * N - 1]
+    jac = solver.mpc_jacobian(ins, it, N, rows, wrt=[0, 15], of="s")
+    unit = solver.unit_seeds(N, rows, of="s")
+    full = solver.mpc_backward_multi(ins, it, None, N, grad_s=unit)
+    cost = solver.mpc_jacobian(ins, it, N, None, wrt=[13, 15], of="objective")
+    one = solver.mpc_backward(ins, it, None, N, grad_objective=torch.ones(C.BATCH, dtype=torch.float64, device="cuda"))
+    torch.cuda.synchronize()
+    assert unit.shape == (3, 16 * N) and torch.equal(unit.sum(1), torch.ones(3, dtype=torch.float64, device="cuda"))
+    assert jac[0].shape == (C.BATCH, 3, 12) and jac[15].shape == (C.BATCH, 3, 3)
+    assert torch.equal(jac[0], full[0]) and torch.equal(jac[15], full[15])
+    assert all(jac[i] is None for i in range(17) if i not in (0, 15))
+    assert cost[13].shape == (C.BATCH, 1, ins[13].shape[1])
+    assert torch.equal(cost[13][:, 0], one[13]) and torch.equal(cost[15][:, 0], one[15])
+    with pytest.raises(ValueError, match="of"):
+        solver.mpc_jacobian(ins, it, N, rows, wrt=[0], of="mu")
+    with pytest.raises(ValueError, match="rows"):
+        solver.unit_seeds(N, [16 * N], of="z")
+
+
+def test_mpc_backward_with_grad_objective_replays_from_a_hip_graph():
+    _native.prepare_device()
+    N, K = 10, 5
+    ins, _, it = _dev_case(N, "random", K)
+    gJ = _dev_seeds(N)["objective"]
+    eager = [t.clone() for t in solver.mpc_backward(ins, it, None, N, grad_objective=gJ)]
+    outs = [torch.empty_like(t) for t in eager]
+    ws = torch.empty(_native.lib().srbd_mpc_backward_workspace_doubles(N, C.BATCH), dtype=torch.float64, device="cuda")
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        solver.mpc_backward(ins, it, None, N, outputs=outs, workspace=ws, grad_objective=gJ)  # warm-up on a side stream
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        solver.mpc_backward(ins, it, None, N, outputs=outs, workspace=ws, grad_objective=gJ)
+    for t in outs:
+        t.fill_(float("nan"))
+    graph.replay()
+    torch.cuda.synchronize()
+    for i, name in enumerate(layout.FORMER_IN_NAMES):
+        assert torch.equal(outs[i], eager[i]), name
+
+
+# ---- 8. the controller ----------------------------------------------------------------------------
+
+def _cost_controller(gait, differentiable=True):
+    from tests.test_gpu_step_backward import _step_controller
+    c, _ = _step_controller(10, gait, differentiable=differentiable)
+    c.cfg.compute_cost = True
+    return c
+
+
+def _cotangents(B, seed):
+    rng = np.random.default_rng(seed)
+    return (torch.from_numpy(rng.standard_normal((B, 2, 6)).astype(np.float32)).cuda(),
+            torch.from_numpy(rng.standard_normal(B).astype(np.float32)).cuda())
+
+
+@pytest.mark.parametrize("gait", [True, False], ids=["gait", "table"])
+def test_controller_backward_with_grad_cost_is_the_hand_chain(gait):
+    N, B = 10, 16
+    c = _cost_controller(gait)
+    wrench, cost = (t.clone() for t in c.run())
+    assert cost.abs().max() > 0
+    gw, gc = _cotangents(B, 6100)
+    rec = c._step_record
+    it = list(c.solution[:4])
+    names = tuple(n for n in _native.PREP_GRAD_NAMES if not (gait and n == "contact_table"))
+    gJ = gc.double()
+    for wrt in (names, ("dt_mpc", "residual_lin_accel"), ("desired_velocity_b",)):
+        fin = solver.mpc_backward(c.former_inputs, it, None, N, grad_objective=gJ)
+        hand = solver.prepare_inputs_backward(rec.prep, fin, N, B, wrt)
+        st = _status(B)
+        got = c.backward(grad_cost=gc, wrt=wrt, status=st)
+        torch.cuda.synchronize()
+        assert torch.all(st == 0) and set(got) == set(wrt)
+        for n in wrt:
+            assert torch.equal(got[n], hand[n]), n
+            assert torch.isfinite(got[n]).all(), n
+    # both cotangents: the single hand chain with both seeds, bit for bit; the two separate calls, to FP32 stores
+    seed, direct = solver.u0_wrench_backward(c.solution[0], rec.tensors["rotation_body"], gw, N)
+    fin = solver.mpc_backward(c.former_inputs, it, seed, N, grad_objective=gJ)
+    hand = solver.prepare_inputs_backward(rec.prep, fin, N, B, names, grad_rotation_body_direct=direct)
+    both, only_w, only_c = c.backward(gw, grad_cost=gc), c.backward(gw), c.backward(grad_cost=gc)
+    torch.cuda.synchronize()
+    for n in names:
+        assert torch.equal(both[n], hand[n]), n
+        a, b = only_w[n].double(), only_c[n].double()
+        err = (both[n].double() - (a + b)).abs().max().item()
+        scale = (a.abs() + b.abs()).max().item()
+        assert err <= 1e-6 * scale, (n, err, scale)
+    assert torch.equal(c.foot_wrench, wrench) and torch.equal(c.cost, cost)  # backward leaves the step's outputs alone
+    plain = _cost_controller(gait, differentiable=False)
+    w2, c2 = plain.run()
+    assert torch.equal(w2, wrench) and torch.equal(c2, cost)  # and recording a step changes no bit of run()
+    c.cfg.compute_cost = False
+    with pytest.raises(RuntimeError, match="compute_cost"):
+        c.backward(grad_cost=gc)
+    with pytest.raises(RuntimeError, match="compute_cost"):
+        c.run_autograd(return_cost=True)
+
+
+def test_run_autograd_with_the_cost_gives_backwards_gradients():
+    B = 16
+    c = _cost_controller(True)
+    names = ("residual_lin_accel", "dt_mpc", "rotation_body")
+    src = {"residual_lin_accel": c.residual_lin_accel, "dt_mpc": c.dt_mpc,
+           "rotation_body": c.state_estimate_data.rotation_body}
+    leaves = {n: src[n].clone().requires_grad_(True) for n in names}
+    w, cost = c.run_autograd(return_cost=True, **leaves)
+    assert w.requires_grad and cost.requires_grad and cost.shape == (B,) and cost.dtype == torch.float32
+    assert torch.equal(w.detach(), c.foot_wrench) and torch.equal(cost.detach(), c.cost)
+    gw, gc = _cotangents(B, 6200)
+    want_both = {n: t.clone() for n, t in c.backward(gw, grad_cost=gc, wrt=names).items()}
+    want_cost = {n: t.clone() for n, t in c.backward(grad_cost=gc, wrt=names).items()}
+    c.run()  # a later step does not invalidate the graph
+    g_both = torch.autograd.grad((w * gw).sum() + (cost * gc).sum(), [leaves[n] for n in names], retain_graph=True)
+    g_cost = torch.autograd.grad((cost * gc).sum(), [leaves[n] for n in names])
+    torch.cuda.synchronize()
+    for n, a, b in zip(names, g_both, g_cost):
+        assert torch.equal(a, want_both[n]) and torch.equal(b, want_cost[n]), n
+        assert a.shape == leaves[n].shape and b.abs().max() > 0, n
+    # the example of the documentation
+    a_lin, dt = leaves["residual_lin_accel"], leaves["dt_mpc"]
+    w2, cost2 = c.run_autograd(return_cost=True, residual_lin_accel=a_lin, dt_mpc=dt)
+    g_lin, g_dt = torch.autograd.grad(cost2.sum() + w2.square().sum(), [a_lin, dt])
+    assert g_lin.shape == a_lin.shape and g_dt.shape == dt.shape and torch.isfinite(g_lin).all()
+    w3 = c.run_autograd(dt_mpc=dt)  # without return_cost: the wrench alone, as before
+    assert isinstance(w3, torch.Tensor) and w3.shape == (B, 2, 6)
