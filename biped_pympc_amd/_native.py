@@ -41,137 +41,9 @@ def lib() -> ctypes.CDLL:
     L = ctypes.CDLL(path)
     if os.environ.get("SRBD_LIB"):  # an earlier build (A/B runs): bind what it exports
         L = _Tolerant(L)
-    L.srbd_abi_version.restype = ctypes.c_int
-    L.srbd_last_error.restype = ctypes.c_char_p
-    L.srbd_build_id.restype = ctypes.c_char_p
-    L.srbd_solver_lds_bytes.restype = ctypes.c_size_t
-    L.srbd_solver_lds_bytes.argtypes = [ctypes.c_int]
-    L.srbd_mpc_workspace_doubles.restype = ctypes.c_size_t
-    L.srbd_mpc_workspace_doubles.argtypes = [ctypes.c_int, ctypes.c_int]
-    P = ctypes.POINTER(_c_dp)
-    L.srbd_qp_former.restype = ctypes.c_int
-    L.srbd_qp_former.argtypes = [ctypes.c_int, ctypes.c_int, P, P, ctypes.c_void_p]
-    L.srbd_pdipm.restype = ctypes.c_int
-    L.srbd_pdipm.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, P, P, ctypes.c_void_p]
-    L.srbd_pdipm_cold.restype = ctypes.c_int
-    L.srbd_pdipm_cold.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, P, P,
-                                  ctypes.c_void_p]
-    L.srbd_pdipm_ccs.restype = ctypes.c_int
-    L.srbd_pdipm_ccs.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, P, P, ctypes.c_void_p]
-    L.srbd_mpc_solve.restype = ctypes.c_int
-    L.srbd_mpc_solve.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, P,
-                                 ctypes.c_void_p, P, ctypes.c_void_p]
-    L.srbd_mpc_solve_fused.restype = ctypes.c_int
-    L.srbd_mpc_solve_fused.argtypes = L.srbd_mpc_solve.argtypes
-    L.srbd_mpc_solve_fused_ex.restype = ctypes.c_int
-    L.srbd_mpc_solve_fused_ex.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, P,
-                                          ctypes.c_void_p, P, _c_dp, ctypes.c_void_p]
-    L.srbd_pdipm_ex.restype = ctypes.c_int
-    L.srbd_pdipm_ex.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, P, P,
-                                _c_dp, ctypes.c_void_p]
-    # the *_info entry points: srbd_solve_info* in place of the status pointer
-    IP = ctypes.POINTER(SolveInfo)
-    L.srbd_pdipm_info.restype = ctypes.c_int
-    L.srbd_pdipm_info.argtypes = L.srbd_pdipm_ex.argtypes[:-2] + [IP, ctypes.c_void_p]
-    L.srbd_mpc_solve_fused_info.restype = ctypes.c_int
-    L.srbd_mpc_solve_fused_info.argtypes = L.srbd_mpc_solve_fused_ex.argtypes[:-2] + [IP, ctypes.c_void_p]
-    L.srbd_prepare_device.restype = ctypes.c_int
-    L.srbd_prepare_device.argtypes = []
-    L.srbd_release_device.restype = ctypes.c_int
-    L.srbd_release_device.argtypes = []
-    L.srbd_set_scratch_slots.restype = ctypes.c_int
-    L.srbd_set_scratch_slots.argtypes = [ctypes.c_int]
-    L.srbd_scratch_pool_bytes.restype = ctypes.c_size_t
-    L.srbd_scratch_pool_bytes.argtypes = []
-    L.srbd_scratch_pool_slots.restype = ctypes.c_int
-    L.srbd_scratch_pool_slots.argtypes = []
-    L.srbd_scratch_slot_bytes.restype = ctypes.c_size_t
-    L.srbd_scratch_slot_bytes.argtypes = []
-    L.srbd_evaluate_qp_former.restype = ctypes.c_float
-    L.srbd_evaluate_qp_former.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                          ctypes.c_void_p, ctypes.c_int]
-    L.srbd_evaluate_pdipm.restype = ctypes.c_float
-    L.srbd_evaluate_pdipm.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                      ctypes.c_void_p, ctypes.c_int]
-    L.srbd_set_solver_path.restype = ctypes.c_int
-    L.srbd_set_solver_path.argtypes = [ctypes.c_int]
-    L.srbd_get_solver_path.restype = ctypes.c_int
-    L.srbd_get_solver_path.argtypes = []
-    L.srbd_set_refinement.restype = ctypes.c_int
-    L.srbd_set_refinement.argtypes = [ctypes.c_int]
-    L.srbd_get_refinement.restype = ctypes.c_int
-    L.srbd_get_refinement.argtypes = []
-    L.srbd_set_refinement_policy.restype = ctypes.c_int
-    L.srbd_set_refinement_policy.argtypes = [ctypes.c_int, ctypes.c_double]
-    L.srbd_pattern_ccs.restype = ctypes.c_int
-    L.srbd_pattern_ccs.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
-                                   ctypes.POINTER(ctypes.c_int)]
-    L.srbd_prepare_inputs.restype = ctypes.c_int
-    L.srbd_prepare_inputs.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(MPCPrep), P, ctypes.c_void_p]
-    L.srbd_mpc_step.restype = ctypes.c_int
-    L.srbd_mpc_step.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.POINTER(MPCPrep),
-                                P, P, _c_dp, ctypes.c_int, _c_dp, _c_dp, _c_dp, ctypes.c_void_p]
-    L.srbd_mpc_step_ex.restype = ctypes.c_int
-    L.srbd_mpc_step_ex.argtypes = L.srbd_mpc_step.argtypes[:-1] + [_c_dp, ctypes.c_void_p]
-    L.srbd_mpc_step_info.restype = ctypes.c_int
-    L.srbd_mpc_step_info.argtypes = L.srbd_mpc_step.argtypes[:-1] + [IP, ctypes.c_void_p]
-    L.srbd_u0_wrench.restype = ctypes.c_int
-    L.srbd_u0_wrench.argtypes = [ctypes.c_int, ctypes.c_int, _c_dp, _c_dp, _c_dp, ctypes.c_void_p]
-    L.srbd_u0_wrench_torque.restype = ctypes.c_int
-    L.srbd_u0_wrench_torque.argtypes = [ctypes.c_int, ctypes.c_int, _c_dp, _c_dp, _c_dp, ctypes.c_int, _c_dp,
-                                        _c_dp, _c_dp, ctypes.c_void_p]
-    L.srbd_dense_scatter.restype = ctypes.c_int
-    L.srbd_dense_scatter.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp, _c_dp,
-                                     ctypes.c_void_p]
-    # the backward pass (adjoint KKT solve, former VJP)
-    L.srbd_pdipm_backward.restype = ctypes.c_int
-    L.srbd_pdipm_backward.argtypes = [ctypes.c_int, ctypes.c_int, P, _c_dp, P, _c_dp, ctypes.c_void_p]
-    L.srbd_qp_former_backward.restype = ctypes.c_int
-    L.srbd_qp_former_backward.argtypes = [ctypes.c_int, ctypes.c_int, P, P, P, ctypes.c_void_p]
-    L.srbd_mpc_backward_workspace_doubles.restype = ctypes.c_size_t
-    L.srbd_mpc_backward_workspace_doubles.argtypes = [ctypes.c_int, ctypes.c_int]
-    L.srbd_mpc_backward.restype = ctypes.c_int
-    L.srbd_mpc_backward.argtypes = [ctypes.c_int, ctypes.c_int, P, P, _c_dp, _c_dp, P, _c_dp, ctypes.c_void_p]
-    # several seeds at one iterate (one factorisation, M solves): Jacobians and the u0 feedback gain
-    L.srbd_pdipm_backward_multi.restype = ctypes.c_int
-    L.srbd_pdipm_backward_multi.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, P, _c_dp, ctypes.c_size_t, P,
-                                            _c_dp, ctypes.c_void_p]
-    L.srbd_qp_former_backward_multi.restype = ctypes.c_int
-    L.srbd_qp_former_backward_multi.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, P, P, P, ctypes.c_void_p]
-    L.srbd_former_grad_deps.restype = ctypes.c_uint
-    L.srbd_former_grad_deps.argtypes = [ctypes.c_int]
-    L.srbd_mpc_backward_multi_workspace_doubles.restype = ctypes.c_size_t
-    L.srbd_mpc_backward_multi_workspace_doubles.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint]
-    L.srbd_mpc_backward_multi.restype = ctypes.c_int
-    L.srbd_mpc_backward_multi.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, P, P, _c_dp, ctypes.c_size_t,
-                                          _c_dp, P, _c_dp, ctypes.c_void_p]
-    # cotangents of every output of a solve (x, s, z, y, objective): srbd_backward_seeds in place of grad_x
-    SP = ctypes.POINTER(BackwardSeeds)
-    L.srbd_pdipm_backward_seeds.restype = ctypes.c_int
-    L.srbd_pdipm_backward_seeds.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, P, SP, P, _c_dp, ctypes.c_void_p]
-    L.srbd_mpc_backward_seeds.restype = ctypes.c_int
-    L.srbd_mpc_backward_seeds.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, P, P, SP, _c_dp, P, _c_dp,
-                                          ctypes.c_void_p]
-    # the backward pass of the controller step's FP32 ends: wrench / torque VJP, input-preparation VJP, the chain
-    L.srbd_u0_wrench_backward.restype = ctypes.c_int
-    L.srbd_u0_wrench_backward.argtypes = [ctypes.c_int, ctypes.c_int, _c_dp, _c_dp, _c_dp, ctypes.c_int, _c_dp, _c_dp,
-                                          _c_dp, _c_dp, _c_dp, ctypes.c_void_p]
-    L.srbd_prepare_inputs_backward.restype = ctypes.c_int
-    L.srbd_prepare_inputs_backward.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(MPCPrep), P, _c_dp, _c_dp,
-                                               _c_dp, P, ctypes.c_void_p]
-    L.srbd_prep_grad_deps.restype = ctypes.c_uint
-    L.srbd_prep_grad_deps.argtypes = [ctypes.c_int]
-    L.srbd_mpc_step_backward_workspace_doubles.restype = ctypes.c_size_t
-    L.srbd_mpc_step_backward_workspace_doubles.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint]
-    L.srbd_mpc_step_backward.restype = ctypes.c_int
-    L.srbd_mpc_step_backward.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(MPCPrep), P, P, _c_dp, ctypes.c_int,
-                                         _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, P, _c_dp, ctypes.c_void_p]
-    # ... with the cotangent of the step's MPC cost (grad_cost after grad_wrench)
-    L.srbd_mpc_step_backward_cost_workspace_doubles.restype = ctypes.c_size_t
-    L.srbd_mpc_step_backward_cost_workspace_doubles.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint]
-    L.srbd_mpc_step_backward_cost.restype = ctypes.c_int
-    L.srbd_mpc_step_backward_cost.argtypes = (L.srbd_mpc_step_backward.argtypes[:6] + [_c_dp]
-                                              + L.srbd_mpc_step_backward.argtypes[6:])
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)  # a plain CDLL raises for a missing symbol; _Tolerant binds a raising stub
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -212,11 +84,15 @@ class _Tolerant:
             return stub
 
 
+# the leading fields of srbd_mpc_prep: the controller reads them off its state estimate and its command
+STATE_FIELDS = ("root_euler", "root_position", "root_angular_velocity_w", "root_velocity_w", "rotation_body",
+                "foot_position")
+COMMAND_FIELDS = ("desired_velocity_b", "desired_angular_velocity_b", "desired_height")
+
+
 class MPCPrep(ctypes.Structure):
     """ctypes mirror of ``srbd_mpc_prep`` (include/srbd_mpc.h); device pointers as void*."""
-    _fields_ = [(n, _c_dp) for n in (
-        "root_euler", "root_position", "root_angular_velocity_w", "root_velocity_w", "rotation_body",
-        "foot_position", "desired_velocity_b", "desired_angular_velocity_b", "desired_height",
+    _fields_ = [(n, _c_dp) for n in STATE_FIELDS + COMMAND_FIELDS + (
         "world_position_desired", "yaw_desired", "first_run", "gait_phase", "ssp_durations",
         "dsp_durations", "contact_table", "dt_mpc", "residual_lin_accel", "residual_ang_accel")] + [
         ("I_body", ctypes.c_float * 9), ("mass", ctypes.c_double), ("mu", ctypes.c_double),
@@ -245,6 +121,78 @@ def solve_info(status=None, objective=None, objective_f32=None):
     if status is None and objective is None and objective_f32 is None:
         return None
     return SolveInfo(status, objective, objective_f32)
+
+
+# The C signatures lib() binds, name -> (restype, argtypes), each written out as include/srbd_mpc.h declares it
+# (tests/test_native_abi.py counts the parameters against the header). I, D, Z, U: int, double, size_t,
+# unsigned; V: a device pointer or the hipStream_t; A: a host array of device pointers.
+_I, _D, _Z, _U, _V = ctypes.c_int, ctypes.c_double, ctypes.c_size_t, ctypes.c_uint, ctypes.c_void_p
+_A = ctypes.POINTER(_c_dp)
+_IP = ctypes.POINTER(ctypes.c_int)
+_PREP, _INFO, _SEEDS = ctypes.POINTER(MPCPrep), ctypes.POINTER(SolveInfo), ctypes.POINTER(BackwardSeeds)
+SIGNATURES = {
+    "srbd_abi_version": (_I, []),
+    "srbd_last_error": (ctypes.c_char_p, []),
+    "srbd_build_id": (ctypes.c_char_p, []),
+    "srbd_evaluate_qp_former": (ctypes.c_float, [_I, _V, _V, _V, _I]),
+    "srbd_evaluate_pdipm": (ctypes.c_float, [_I, _I, _V, _V, _V, _I]),
+    # forward: former, solver (plain / status word / extras struct), the fused solve
+    "srbd_qp_former": (_I, [_I, _I, _A, _A, _V]),
+    "srbd_pdipm": (_I, [_I, _I, _I, _A, _A, _V]),
+    "srbd_pdipm_cold": (_I, [_I, _I, _I, _D, _A, _A, _V]),
+    "srbd_pdipm_ccs": (_I, [_I, _I, _I, _A, _A, _V]),
+    "srbd_pdipm_ex": (_I, [_I, _I, _I, _I, _D, _A, _A, _V, _V]),
+    "srbd_pdipm_info": (_I, [_I, _I, _I, _I, _D, _A, _A, _INFO, _V]),
+    "srbd_mpc_workspace_doubles": (_Z, [_I, _I]),
+    "srbd_mpc_solve": (_I, [_I, _I, _I, _D, _A, _V, _A, _V]),
+    "srbd_mpc_solve_fused": (_I, [_I, _I, _I, _D, _A, _V, _A, _V]),
+    "srbd_mpc_solve_fused_ex": (_I, [_I, _I, _I, _D, _A, _V, _A, _V, _V]),
+    "srbd_mpc_solve_fused_info": (_I, [_I, _I, _I, _D, _A, _V, _A, _INFO, _V]),
+    # per-device state and host-only introspection
+    "srbd_solver_lds_bytes": (_Z, [_I]),
+    "srbd_set_solver_path": (_I, [_I]),
+    "srbd_get_solver_path": (_I, []),
+    "srbd_set_refinement": (_I, [_I]),
+    "srbd_get_refinement": (_I, []),
+    "srbd_set_refinement_policy": (_I, [_I, _D]),
+    "srbd_prepare_device": (_I, []),
+    "srbd_release_device": (_I, []),
+    "srbd_set_scratch_slots": (_I, [_I]),
+    "srbd_scratch_pool_bytes": (_Z, []),
+    "srbd_scratch_pool_slots": (_I, []),
+    "srbd_scratch_slot_bytes": (_Z, []),
+    "srbd_pattern_ccs": (_I, [_I, _I, _IP, _IP]),
+    # the controller step and its parts
+    "srbd_prepare_inputs": (_I, [_I, _I, _PREP, _A, _V]),
+    "srbd_mpc_step": (_I, [_I, _I, _I, _D, _PREP, _A, _A, _V, _I, _V, _V, _V, _V]),
+    "srbd_mpc_step_ex": (_I, [_I, _I, _I, _D, _PREP, _A, _A, _V, _I, _V, _V, _V, _V, _V]),
+    "srbd_mpc_step_info": (_I, [_I, _I, _I, _D, _PREP, _A, _A, _V, _I, _V, _V, _V, _INFO, _V]),
+    "srbd_u0_wrench": (_I, [_I, _I, _V, _V, _V, _V]),
+    "srbd_u0_wrench_torque": (_I, [_I, _I, _V, _V, _V, _I, _V, _V, _V, _V]),
+    "srbd_dense_scatter": (_I, [_I, _I, _I, _V, _V, _V, _V]),
+    # the backward pass: adjoint KKT solve, former VJP and their composition, for grad_x alone (one seed / M
+    # seeds) and for cotangents of every output of a solve (srbd_backward_seeds)
+    "srbd_pdipm_backward": (_I, [_I, _I, _A, _V, _A, _V, _V]),
+    "srbd_pdipm_backward_multi": (_I, [_I, _I, _I, _A, _V, _Z, _A, _V, _V]),
+    "srbd_pdipm_backward_seeds": (_I, [_I, _I, _I, _A, _SEEDS, _A, _V, _V]),
+    "srbd_qp_former_backward": (_I, [_I, _I, _A, _A, _A, _V]),
+    "srbd_qp_former_backward_multi": (_I, [_I, _I, _I, _A, _A, _A, _V]),
+    "srbd_former_grad_deps": (_U, [_I]),
+    "srbd_mpc_backward_workspace_doubles": (_Z, [_I, _I]),
+    "srbd_mpc_backward_multi_workspace_doubles": (_Z, [_I, _I, _I, _U]),
+    "srbd_mpc_backward": (_I, [_I, _I, _A, _A, _V, _V, _A, _V, _V]),
+    "srbd_mpc_backward_multi": (_I, [_I, _I, _I, _A, _A, _V, _Z, _V, _A, _V, _V]),
+    "srbd_mpc_backward_seeds": (_I, [_I, _I, _I, _A, _A, _SEEDS, _V, _A, _V, _V]),
+    # the backward pass of the controller step's FP32 ends: wrench / torque VJP, input-preparation VJP, the chain
+    # (the _cost entry takes grad_cost after grad_wrench)
+    "srbd_u0_wrench_backward": (_I, [_I, _I, _V, _V, _V, _I, _V, _V, _V, _V, _V, _V]),
+    "srbd_prepare_inputs_backward": (_I, [_I, _I, _PREP, _A, _V, _V, _V, _A, _V]),
+    "srbd_prep_grad_deps": (_U, [_I]),
+    "srbd_mpc_step_backward_workspace_doubles": (_Z, [_I, _I, _U]),
+    "srbd_mpc_step_backward": (_I, [_I, _I, _PREP, _A, _A, _V, _I, _V, _V, _V, _V, _V, _V, _A, _V, _V]),
+    "srbd_mpc_step_backward_cost_workspace_doubles": (_Z, [_I, _I, _U]),
+    "srbd_mpc_step_backward_cost": (_I, [_I, _I, _PREP, _A, _A, _V, _V, _I, _V, _V, _V, _V, _V, _V, _A, _V, _V]),
+}
 
 
 def ptr_array(ptrs) -> ctypes.Array:

@@ -231,10 +231,9 @@ class MPCControllerHIP(BaseMPCController):
             return used[name]
 
         p = _native.MPCPrep()
-        for name in ("root_euler", "root_position", "root_angular_velocity_w", "root_velocity_w",
-                     "rotation_body", "foot_position"):
+        for name in _native.STATE_FIELDS:
             setattr(p, name, ptr(src(st, name)))
-        for name in ("desired_velocity_b", "desired_angular_velocity_b", "desired_height"):
+        for name in _native.COMMAND_FIELDS:
             setattr(p, name, ptr(src(ds, name)))
         for name in ("world_position_desired", "yaw_desired"):  # updated in place by the kernel
             t = getattr(self, name)
@@ -278,34 +277,28 @@ class MPCControllerHIP(BaseMPCController):
         return self.former_inputs
 
     def _step(self, p: _native.MPCPrep, J: torch.Tensor | None, cb: torch.Tensor | None) -> None:
-        """One srbd_mpc_step launch: prep -> fused former + PDIPM -> wrench (-> torque)."""
+        """One srbd_mpc_step_info launch: prep -> fused former + PDIPM -> wrench (-> torque)."""
         N, B = self.horizon_length, self.num_envs
         outs = (_native.ptr_array([t.data_ptr() for t in self.buffers.outputs])
                 if self.cfg.keep_solution else None)
         fin = (_native.ptr_array([t.data_ptr() for t in self.former_inputs])
                if self.cfg.keep_solution else None)
-        args = (N, self.cfg.pdipm_iterations, B, float(self.cfg.y0), ctypes.byref(p), fin, outs,
-                self.foot_wrench.data_ptr(), 0 if J is None else J.shape[3], None if J is None else J.data_ptr(),
-                None if cb is None else cb.data_ptr(), None if J is None else self.tau.data_ptr())
-        st = solver._check_status(self.status, B, "MPCControllerHIP.status")
+        st = solver._tensor_ptr(self.status, torch.int32, B, "MPCControllerHIP", "status")
+        cost = (solver._tensor_ptr(self.cost, torch.float32, (B,), "MPCControllerHIP", "cost")
+                if self.cfg.compute_cost else None)
         if self.cfg.differentiable:  # the step clears first_run; its backward pass needs the flag it read
             self._first_run_prev.copy_(self.first_run)
-        if self.cfg.compute_cost:
-            rc = _native.lib().srbd_mpc_step_info(*args, _native.solve_info(st, None, self._cost_ptr()),
-                                                  solver._stream_ptr())
-        elif st is not None:
-            rc = _native.lib().srbd_mpc_step_ex(*args, st, solver._stream_ptr())
-        else:
-            rc = _native.lib().srbd_mpc_step(*args, solver._stream_ptr())
+        rc = _native.lib().srbd_mpc_step_info(
+            N, self.cfg.pdipm_iterations, B, float(self.cfg.y0), ctypes.byref(p), fin, outs,
+            self.foot_wrench.data_ptr(), 0 if J is None else J.shape[3], None if J is None else J.data_ptr(),
+            None if cb is None else cb.data_ptr(), None if J is None else self.tau.data_ptr(),
+            _native.solve_info(st, None, cost), solver._stream_ptr())  # (a NULL struct without status and cost)
         _native.check(rc, "srbd_mpc_step")
         self.solution = self.buffers.outputs if self.cfg.keep_solution else None
         self._step_record = None
         if self.cfg.differentiable and self.cfg.keep_solution and self._step_tensors is not None:
             self._step_record = _StepRecord(p, self._step_tensors, self._first_run_prev, self.former_inputs,
                                             list(self.solution[:4]), N, B)
-
-    def _cost_ptr(self) -> int:
-        return solver._check_objective(self.cost, self.num_envs, "MPCControllerHIP.cost", torch.float32, "cost")
 
     def run(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """MPCControllerCusadi.run (mpc_controller_cusadi.py:43-205): (foot_wrench (B,2,6) f32, cost);
@@ -548,9 +541,8 @@ class GraphedMPCStep:
         """(name, storage pointer) of every tensor the step reads or updates, plus the constants the
         graph bakes in -- without converting or synchronising anything."""
         c, st, ds = self.c, self.c.state_estimate_data, self.c.desired_state_data
-        src = [(n, getattr(st, n)) for n in ("root_euler", "root_position", "root_angular_velocity_w",
-                                             "root_velocity_w", "rotation_body", "foot_position")]
-        src += [(n, getattr(ds, n)) for n in ("desired_velocity_b", "desired_angular_velocity_b", "desired_height")]
+        src = [(n, getattr(st, n)) for n in _native.STATE_FIELDS]
+        src += [(n, getattr(ds, n)) for n in _native.COMMAND_FIELDS]
         src += [(n, getattr(c, n)) for n in ("world_position_desired", "yaw_desired", "first_run", "dt_mpc",
                                              "residual_lin_accel", "residual_ang_accel")]
         if c._gait is not None:

@@ -18,64 +18,75 @@ def _stream_ptr() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
-def _check_batch(tensors, widths, B: int, what: str):
-    for i, (t, w) in enumerate(zip(tensors, widths)):
-        if t is None:
-            continue
-        if not t.is_cuda or t.dtype != torch.float64:
-            raise TypeError(f"{what}: input {i} must be a CUDA float64 tensor")
-        if t.device.index != torch.cuda.current_device():  # launches go to the current device's stream
-            raise ValueError(f"{what}: input {i} is on {t.device}, the current device is "
-                             f"cuda:{torch.cuda.current_device()}")
-        if t.numel() != B * w:
-            raise ValueError(f"{what}: input {i} has {t.numel()} elements, expected {B}x{w}")
-        if not t.is_contiguous():
-            raise ValueError(f"{what}: input {i} must be contiguous (CusADi row layout)")
+def _tensor_ptr(t, dtype, shape, what: str, name, device: int | None = None):
+    """The one check of a tensor argument: None -> None, else the device pointer of ``t`` once it is a CUDA
+    tensor of ``dtype`` on the current device (launches go to its stream), contiguous, and of ``shape`` -- a
+    tuple, an element count (the CusADi row layout: any shape of that many elements), or None when the
+    caller reads the shape itself. ``name``: the argument's name, or its index in a list of inputs.
+    ``device``: the current device's index, for a caller that looked it up once for many tensors."""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
+        raise TypeError(f"{what}: {_arg_name(name)} must be a CUDA {dtype} tensor")
+    if t.device.index != (torch.cuda.current_device() if device is None else device):
+        raise ValueError(f"{what}: {_arg_name(name)} is on {t.device}, the current device is "
+                         f"cuda:{torch.cuda.current_device()}")
+    if shape is not None and (t.numel() != shape if isinstance(shape, int) else tuple(t.shape) != tuple(shape)):
+        expected = f"{shape} elements" if isinstance(shape, int) else f"shape {tuple(shape)}"
+        raise ValueError(f"{what}: {_arg_name(name)} must have {expected}, got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what}: {_arg_name(name)} must be contiguous")
+    return t.data_ptr()
+
+
+def _arg_name(name) -> str:
+    return name if isinstance(name, str) else f"input {name}"
+
+
+def _check_batch(tensors, widths, B: int, what: str) -> list:
+    """float64 tensors of B rows of their width (None entries allowed) -> their pointers (None for None)."""
+    dev = torch.cuda.current_device()
+    return [_tensor_ptr(t, torch.float64, B * w, what, i, dev) for i, (t, w) in enumerate(zip(tensors, widths))]
+
+
+def _ptrs(tensors):
+    return _native.ptr_array([t.data_ptr() if t is not None else 0 for t in tensors])
 
 
 def qp_former(inputs: list[torch.Tensor], N: int, outputs: list[torch.Tensor] | None = None):
     """17 former inputs -> [H, f, A, b, G, d] nonzeros (B, nnz) (srbd_constraints.py:20-81)."""
     d = Dims(N)
     B = inputs[0].shape[0]
-    _check_batch(inputs, d.former_in_nnz, B, "qp_former")
+    ins = _check_batch(inputs, d.former_in_nnz, B, "qp_former")
     if outputs is None:
         outputs = [torch.empty((B, w), dtype=torch.float64, device=inputs[0].device)
                    for w in d.former_out_nnz]
-    _check_batch(outputs, d.former_out_nnz, B, "qp_former outputs")
-    L = _native.lib()
-    rc = L.srbd_qp_former(N, B, _native.ptr_array([t.data_ptr() for t in inputs]),
-                          _native.ptr_array([t.data_ptr() for t in outputs]), _stream_ptr())
+    outp = _check_batch(outputs, d.former_out_nnz, B, "qp_former outputs")
+    rc = _native.lib().srbd_qp_former(N, B, _native.ptr_array(ins), _native.ptr_array(outp), _stream_ptr())
     _native.check(rc, "srbd_qp_former")
     return outputs
 
 
-def _check_status(status, B: int, what: str):
-    """status: None, or an int32 (B,) CUDA tensor on the current device for the per-problem status
-    word (include/srbd_mpc.h SRBD_STATUS_*: 1 non-finite result, 2 step length at its floor in the
-    last iteration, 4 general fallback taken)."""
-    if status is None:
-        return None
-    if (not status.is_cuda or status.dtype != torch.int32 or status.numel() != B or not status.is_contiguous()
-            or status.device.index != torch.cuda.current_device()):
-        raise ValueError(f"{what}: status must be a contiguous int32 CUDA tensor of {B} elements on the current device")
-    return status.data_ptr()
-
-
-def _check_objective(objective, B: int, what: str, dtype=torch.float64, name: str = "objective"):
-    """objective: None, or a contiguous ``dtype`` (B,) CUDA tensor on the current device for the QP
-    objective J = 0.5 x^T H x + f^T x of the returned x (include/srbd_mpc.h srbd_solve_info)."""
-    if objective is None:
-        return None
-    if not isinstance(objective, torch.Tensor) or not objective.is_cuda or objective.dtype != dtype:
-        raise TypeError(f"{what}: {name} must be a CUDA {dtype} tensor")
-    if (objective.dim() != 1 or objective.numel() != B or not objective.is_contiguous()
-            or objective.device.index != torch.cuda.current_device()):
-        raise ValueError(f"{what}: {name} must be a contiguous ({B},) tensor on the current device")
-    return objective.data_ptr()
-
-
 def _alloc_solver_outputs(B: int, N: int, device) -> list[torch.Tensor]:
     return [torch.empty((B, w), dtype=torch.float64, device=device) for w in Dims(N).solver_out_nnz]
+
+
+def _pdipm(what: str, qp, start, init_mode: int, N: int, n_iter: int, y0: float, outputs, status, objective):
+    """``srbd_pdipm_info`` for ``pdipm`` (init_mode 0: from the iterate, 1: cold start with y = y0) and
+    ``pdipm_ccs`` (2: from x_init); ``start`` holds solver inputs 6..9. Without ``status`` and ``objective`` the
+    extras struct is NULL: the entry then runs what srbd_pdipm / _cold / _ccs run."""
+    d = Dims(N)
+    B = qp[0].shape[0]
+    ins = _check_batch(list(qp) + list(start), d.solver_in_nnz, B, what)
+    obj = _tensor_ptr(objective, torch.float64, (B,), what, "objective")
+    if outputs is None:
+        outputs = _alloc_solver_outputs(B, N, qp[0].device)
+    outp = _check_batch(outputs, d.solver_out_nnz, B, what + " outputs")
+    st = _tensor_ptr(status, torch.int32, B, what, "status")
+    rc = _native.lib().srbd_pdipm_info(N, n_iter, B, init_mode, float(y0), _native.ptr_array(ins),
+                                       _native.ptr_array(outp), _native.solve_info(st, obj), _stream_ptr())
+    _native.check(rc, "srbd_" + what)
+    return outputs
 
 
 def pdipm(qp: list[torch.Tensor], iterate: list[torch.Tensor] | None, N: int, n_iter: int,
@@ -86,32 +97,13 @@ def pdipm(qp: list[torch.Tensor], iterate: list[torch.Tensor] | None, N: int, n_
     qp: [Q_val, G_val, A_val, f, h, b]; iterate: [x, s, z, y] or None for the GPU caller's cold
     start (x=0, s=max(h,1), z=1, y=y0; mpc_controller_cusadi.py:138-141).
     Returns [x, s, z, y, residuals(4), mu(1)]; ``status`` (int32 (B,), optional) receives the
-    per-problem status word, ``objective`` (float64 (B,), optional) the QP objective
-    0.5 x^T H x + f^T x of the returned x.
+    per-problem status word (include/srbd_mpc.h SRBD_STATUS_*: 1 non-finite result, 2 step length at its
+    floor in the last iteration, 4 general fallback taken), ``objective`` (float64 (B,), optional) the QP
+    objective 0.5 x^T H x + f^T x of the returned x.
     """
-    d = Dims(N)
-    B = qp[0].shape[0]
-    ins = list(qp) + (list(iterate) if iterate is not None else [None] * 4)
-    _check_batch(ins, d.solver_in_nnz, B, "pdipm")
-    obj = _check_objective(objective, B, "pdipm")
-    if outputs is None:
-        outputs = _alloc_solver_outputs(B, N, qp[0].device)
-    _check_batch(outputs, d.solver_out_nnz, B, "pdipm outputs")
-    L = _native.lib()
-    ptrs = _native.ptr_array([t.data_ptr() if t is not None else 0 for t in ins])
-    outp = _native.ptr_array([t.data_ptr() for t in outputs])
-    st = _check_status(status, B, "pdipm")
-    if obj is not None:
-        info = _native.solve_info(st, obj)
-        rc = L.srbd_pdipm_info(N, n_iter, B, 1 if iterate is None else 0, float(y0), ptrs, outp, info, _stream_ptr())
-    elif st is not None:
-        rc = L.srbd_pdipm_ex(N, n_iter, B, 1 if iterate is None else 0, float(y0), ptrs, outp, st, _stream_ptr())
-    elif iterate is None:
-        rc = L.srbd_pdipm_cold(N, n_iter, B, float(y0), ptrs, outp, _stream_ptr())
-    else:
-        rc = L.srbd_pdipm(N, n_iter, B, ptrs, outp, _stream_ptr())
-    _native.check(rc, "srbd_pdipm")
-    return outputs
+    if iterate is None:
+        return _pdipm("pdipm", qp, [None] * 4, 1, N, n_iter, y0, outputs, status, objective)
+    return _pdipm("pdipm", qp, iterate, 0, N, n_iter, y0, outputs, status, objective)
 
 
 def pdipm_ccs(qp: list[torch.Tensor], x_init: torch.Tensor, N: int, n_iter: int,
@@ -122,26 +114,7 @@ def pdipm_ccs(qp: list[torch.Tensor], x_init: torch.Tensor, N: int, n_iter: int,
     (initialize_pdipm_variables, :537-558). qp: [Q_val, G_val, A_val, f, h, b]; x_init (B, 24N).
     Returns [x, s, z, y, residuals(4), mu(1)] (the reference Function returns x); ``status`` and
     ``objective`` as ``pdipm``."""
-    d = Dims(N)
-    B = qp[0].shape[0]
-    ins = list(qp) + [x_init, None, None, None]
-    _check_batch(ins, d.solver_in_nnz, B, "pdipm_ccs")
-    obj = _check_objective(objective, B, "pdipm_ccs")
-    if outputs is None:
-        outputs = _alloc_solver_outputs(B, N, qp[0].device)
-    _check_batch(outputs, d.solver_out_nnz, B, "pdipm_ccs outputs")
-    ptrs = _native.ptr_array([t.data_ptr() if t is not None else 0 for t in ins])
-    outp = _native.ptr_array([t.data_ptr() for t in outputs])
-    st = _check_status(status, B, "pdipm_ccs")
-    if obj is not None:
-        rc = _native.lib().srbd_pdipm_info(N, n_iter, B, 2, 0.0, ptrs, outp, _native.solve_info(st, obj),
-                                           _stream_ptr())
-    elif st is not None:
-        rc = _native.lib().srbd_pdipm_ex(N, n_iter, B, 2, 0.0, ptrs, outp, st, _stream_ptr())
-    else:
-        rc = _native.lib().srbd_pdipm_ccs(N, n_iter, B, ptrs, outp, _stream_ptr())
-    _native.check(rc, "srbd_pdipm_ccs")
-    return outputs
+    return _pdipm("pdipm_ccs", qp, [x_init, None, None, None], 2, N, n_iter, 0.0, outputs, status, objective)
 
 
 class MPCSolveBuffers:
@@ -192,65 +165,55 @@ def mpc_solve(former_inputs: list[torch.Tensor], N: int, n_iter: int, y0: float 
     Equivalent to the GPU caller's step (mpc_controller_cusadi.py:99-169) with the Newton
     iteration count as a runtime argument. Returns [x, s, z, y, residuals, mu].
     ``fused`` (default): one kernel forms the QP in registers / LDS and solves it
-    (``srbd_mpc_solve_fused``; the register-resident step kernel at every N in 2..32, the
+    (``srbd_mpc_solve_fused_info``; the register-resident step kernel at every N in 2..32, the
     LDS-resident step kernel at N = 1): no QP data reaches memory, unless ``keep_qp`` (then f, b, d go to their
     ``buffers.workspace`` slots); ``False`` runs the former and the solver as two kernels with the
-    full QP in the workspace. Both give the same bits. ``status`` (int32 (B,), optional) receives
+    full QP in the workspace (``srbd_mpc_solve``; under a non-auto solver path ``fused`` runs these two
+    kernels as well). Both give the same bits. ``status`` (int32 (B,), optional) receives
     the per-problem status word, ``objective`` (float64 (B,), optional) the QP objective
     0.5 x^T H x + f^T x of the returned x -- the reference's MPC cost -- and ``objective_f32`` (float32
-    (B,), optional) the same value rounded once to float32 (the controller's ``cost``).
+    (B,), optional) the same value rounded once to float32 (the controller's ``cost``); under the auto
+    solver path these three need ``fused``.
     """
     d = Dims(N)
     B = former_inputs[0].shape[0]
-    _check_batch(former_inputs, d.former_in_nnz, B, "mpc_solve")
-    obj = _check_objective(objective, B, "mpc_solve")
-    obj32 = _check_objective(objective_f32, B, "mpc_solve", torch.float32, "objective_f32")
+    ins = _check_batch(former_inputs, d.former_in_nnz, B, "mpc_solve")
+    obj = _tensor_ptr(objective, torch.float64, (B,), "mpc_solve", "objective")
+    obj32 = _tensor_ptr(objective_f32, torch.float32, (B,), "mpc_solve", "objective_f32")
     if buffers is None or buffers.B != B or buffers.N != N:
         buffers = MPCSolveBuffers.allocate(N, B, former_inputs[0].device)
-    _check_batch(buffers.outputs, d.solver_out_nnz, B, "mpc_solve outputs")
+    outp = _check_batch(buffers.outputs, d.solver_out_nnz, B, "mpc_solve outputs")
     if buffers.device != former_inputs[0].device:
         raise ValueError(f"mpc_solve: buffers on {buffers.device}, inputs on {former_inputs[0].device}")
     L = _native.lib()
-    # the fused kernel runs under the auto solver path (any horizon); otherwise the former writes the
-    # whole QP into the workspace for the solver kernel
-    one_kernel = fused and _native.current_solver_path() == 0
-    args = (N, n_iter, B, float(y0), _native.ptr_array([t.data_ptr() for t in former_inputs]),
-            buffers.workspace.data_ptr() if (keep_qp or not one_kernel) else None,
-            _native.ptr_array([t.data_ptr() for t in buffers.outputs]))
-    st = _check_status(status, B, "mpc_solve")
-    info = _native.solve_info(None if obj is None and obj32 is None else st, obj, obj32)
-    if info is not None or st is not None:  # the two-kernel form runs under the non-auto branch alike
-        if not fused and one_kernel:
-            raise ValueError("mpc_solve: status / objective with fused=False needs a non-auto solver path")
-    if info is not None:
-        rc = L.srbd_mpc_solve_fused_info(*args, info, _stream_ptr())
-    elif st is not None:
-        rc = L.srbd_mpc_solve_fused_ex(*args, st, _stream_ptr())
+    # srbd_mpc_solve (no extras) only for the two-kernel form under the auto solver path; the _info entry
+    # runs the fused kernel under that path and the same two kernels, with the extras, under any other
+    auto = _native.current_solver_path() == 0
+    two_kernels = auto and not fused
+    info = _native.solve_info(_tensor_ptr(status, torch.int32, B, "mpc_solve", "status"), obj, obj32)
+    if two_kernels and info is not None:
+        raise ValueError("mpc_solve: status / objective with fused=False needs a non-auto solver path")
+    args = (N, n_iter, B, float(y0), _native.ptr_array(ins),  # (the one fused kernel writes no QP unless asked)
+            buffers.workspace.data_ptr() if (keep_qp or not (auto and fused)) else None, _native.ptr_array(outp))
+    if two_kernels:
+        rc = L.srbd_mpc_solve(*args, _stream_ptr())
     else:
-        rc = (L.srbd_mpc_solve_fused if fused else L.srbd_mpc_solve)(*args, _stream_ptr())
+        rc = L.srbd_mpc_solve_fused_info(*args, info, _stream_ptr())
     _native.check(rc, "srbd_mpc_solve")
     return buffers.outputs
 
 
 # ---- backward pass: gradients of a loss on a solve's outputs through the QP solve and the former ----
+# Every wrapper below builds a srbd_backward_seeds and calls the *_seeds entry; with grad_x alone that entry
+# runs the kernels' x-only instantiation, and one seed per env the single-seed kernel (DESIGN.md 6c).
 
 def _optional_outputs(outputs, widths, B: int, device, what: str, M: int | None = None, want=None):
     """(B, width) outputs, or (B, M, width) for M seeds: None -> those in `want` (default all)
-    allocated; a list -> its tensors, None entries stay unwritten (NULL)."""
+    allocated; a list -> its tensors, None entries stay unwritten (NULL). Returns (list, pointer array)."""
     if outputs is None:
         outputs = [torch.empty((B, w) if M is None else (B, M, w), dtype=torch.float64, device=device)
                    if want is None or i in want else None for i, w in enumerate(widths)]
-    _check_batch(outputs, [(M or 1) * w for w in widths], B, what)
-    return list(outputs)
-
-
-def _ptrs(tensors):
-    return _native.ptr_array([t.data_ptr() if t is not None else 0 for t in tensors])
-
-
-def _require_qp_and_iterate(ins, what: str) -> None:
-    if any(ins[i] is None for i in (0, 1, 2, 6, 7, 8, 9)):
-        raise ValueError(f"{what}: Q_val, G_val, A_val and the iterate x, s, z, y are required")
+    return list(outputs), _native.ptr_array(_check_batch(outputs, [(M or 1) * w for w in widths], B, what))
 
 
 def _workspace(workspace, n: int, device, what: str) -> torch.Tensor:
@@ -274,19 +237,10 @@ def _seed_struct(seeds, B: int, N: int, what: str, multi: bool):
     names = ["grad_" + k for k in _native.SEED_KINDS]
     if all(t is None for t in seeds):
         raise ValueError(f"{what}: no seed given ({', '.join(names)} are all None)")
-    M, shared = 1, None
+    M, shared, ptrs = 1, None, []
     for t, w, name in zip(seeds, _seed_widths(N), names):
-        if t is None:
-            continue
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64:
-            raise TypeError(f"{what}: {name} must be a CUDA float64 tensor")
-        if t.device.index != torch.cuda.current_device():
-            raise ValueError(f"{what}: {name} is on {t.device}, the current device is cuda:{torch.cuda.current_device()}")
-        if not t.is_contiguous():
-            raise ValueError(f"{what}: {name} must be contiguous")
-        if not multi:
-            if t.numel() != B * w or t.shape[0] != B:
-                raise ValueError(f"{what}: {name} must be ({B}, {w}), got {tuple(t.shape)}")
+        ptrs.append(_tensor_ptr(t, torch.float64, None if multi else B * w, what, name))
+        if t is None or not multi:
             continue
         if t.dim() == 2 and t.shape[1] == w and t.shape[0] >= 1:
             m_t, sh_t = t.shape[0], True
@@ -300,12 +254,25 @@ def _seed_struct(seeds, B: int, N: int, what: str, multi: bool):
         elif (m_t, sh_t) != (M, shared):
             raise ValueError(f"{what}: every seed must have the same M and the same sharing; {name} is "
                              f"{tuple(t.shape)}")
-    sd = _native.BackwardSeeds(*[None if t is None else t.data_ptr() for t in seeds], 1 if shared else 0)
-    return sd, M
+    return _native.BackwardSeeds(*ptrs, 1 if shared else 0), M
 
 
-def _only_x(seeds) -> bool:
-    return seeds[0] is not None and all(t is None for t in seeds[1:])
+def _pdipm_backward(what: str, multi: bool, qp, iterate, seeds, N: int, status, outputs):
+    d = Dims(N)
+    B = iterate[0].shape[0]
+    ins = list(qp) + list(iterate)
+    inp = _check_batch(ins, d.solver_in_nnz, B, what)
+    if any(ins[i] is None for i in (0, 1, 2, 6, 7, 8, 9)):
+        raise ValueError(f"{what}: Q_val, G_val, A_val and the iterate x, s, z, y are required")
+    sd, M = _seed_struct(seeds, B, N, what, multi)
+    if seeds[4] is not None and ins[3] is None:
+        raise ValueError(f"{what}: grad_objective needs f (qp[3])")
+    outs, outp = _optional_outputs(outputs, d.former_out_nnz, B, iterate[0].device, what + " outputs",
+                                   M if multi else None)
+    rc = _native.lib().srbd_pdipm_backward_seeds(N, B, M, _native.ptr_array(inp), ctypes.byref(sd), outp,
+                                                 _tensor_ptr(status, torch.int32, B, what, "status"), _stream_ptr())
+    _native.check(rc, "srbd_pdipm_backward_seeds")
+    return outs
 
 
 def pdipm_backward(qp: list, iterate: list[torch.Tensor], grad_x: torch.Tensor | None, N: int,
@@ -315,32 +282,16 @@ def pdipm_backward(qp: list, iterate: list[torch.Tensor], grad_x: torch.Tensor |
     """The adjoint KKT solve at ``iterate`` = [x, s, z, y] of the QP ``qp`` = [Q_val, G_val, A_val, f, h, b]
     (h, b are not read and may be None; f only with ``grad_objective``) for the seed ``grad_x`` = dL/dx
     (B, 24N) and, optionally, the cotangents of the solve's other outputs: ``grad_s`` and ``grad_z`` (B, 16N),
-    ``grad_y`` (B, 14N) and ``grad_objective`` (B,), that of J = 0.5 x^T H x + f^T x. A None seed is zero
-    (``grad_x`` may be None when another is given); with ``grad_x`` alone the result has today's bits.
+    ``grad_y`` (B, 14N) and ``grad_objective`` (B,), that of J = 0.5 x^T H x + f^T x. A None seed is zero: it
+    gives the bits an all-zero tensor gives (``grad_x`` may be None when another is given).
 
     Returns [grad_H, grad_f, grad_A, grad_b, grad_G, grad_d] in qp_former's output order and CCS widths
     (every nonzero is its own parameter). ``outputs``: preallocated tensors, None entries are skipped.
     ``status`` (int32 (B,), optional): _native.STATUS_UNSUPPORTED for a QP that is not stage-invariant
     (its gradients are NaN), STATUS_NONFINITE for a non-finite adjoint. The gradient at a non-converged
     iterate is the exact derivative of the linearised KKT conditions at that iterate (as in qpth)."""
-    d = Dims(N)
-    B = iterate[0].shape[0]
-    seeds = [grad_x, grad_s, grad_z, grad_y, grad_objective]
-    ins = list(qp) + list(iterate)
-    _check_batch(ins + [grad_x], d.solver_in_nnz + (d.nz,), B, "pdipm_backward")
-    _require_qp_and_iterate(ins, "pdipm_backward")
-    outs = _optional_outputs(outputs, d.former_out_nnz, B, iterate[0].device, "pdipm_backward outputs")
-    st = _check_status(status, B, "pdipm_backward")
-    if _only_x(seeds):
-        rc = _native.lib().srbd_pdipm_backward(N, B, _ptrs(ins), grad_x.data_ptr(), _ptrs(outs), st, _stream_ptr())
-        _native.check(rc, "srbd_pdipm_backward")
-        return outs
-    sd, _ = _seed_struct(seeds, B, N, "pdipm_backward", multi=False)
-    if grad_objective is not None and ins[3] is None:
-        raise ValueError("pdipm_backward: grad_objective needs f (qp[3])")
-    rc = _native.lib().srbd_pdipm_backward_seeds(N, B, 1, _ptrs(ins), ctypes.byref(sd), _ptrs(outs), st, _stream_ptr())
-    _native.check(rc, "srbd_pdipm_backward_seeds")
-    return outs
+    return _pdipm_backward("pdipm_backward", False, qp, iterate, [grad_x, grad_s, grad_z, grad_y, grad_objective],
+                           N, status, outputs)
 
 
 def qp_former_backward(former_inputs: list[torch.Tensor], qp_grads: list, N: int, outputs: list | None = None):
@@ -350,12 +301,48 @@ def qp_former_backward(former_inputs: list[torch.Tensor], qp_grads: list, N: int
     ``outputs``: preallocated tensors, None entries are skipped."""
     d = Dims(N)
     B = former_inputs[0].shape[0]
-    _check_batch(former_inputs, d.former_in_nnz, B, "qp_former_backward")
-    _check_batch(qp_grads, d.former_out_nnz, B, "qp_former_backward gradients")
-    outs = _optional_outputs(outputs, d.former_in_nnz, B, former_inputs[0].device, "qp_former_backward outputs")
-    rc = _native.lib().srbd_qp_former_backward(N, B, _ptrs(former_inputs), _ptrs(qp_grads), _ptrs(outs),
+    ins = _check_batch(former_inputs, d.former_in_nnz, B, "qp_former_backward")
+    grads = _check_batch(qp_grads, d.former_out_nnz, B, "qp_former_backward gradients")
+    outs, outp = _optional_outputs(outputs, d.former_in_nnz, B, former_inputs[0].device, "qp_former_backward outputs")
+    rc = _native.lib().srbd_qp_former_backward(N, B, _native.ptr_array(ins), _native.ptr_array(grads), outp,
                                                _stream_ptr())
     _native.check(rc, "srbd_qp_former_backward")
+    return outs
+
+
+def _input_mask(wrt) -> int:
+    mask = 0
+    for i in wrt:
+        if not 0 <= int(i) < 17:
+            raise ValueError(f"wrt: former-input index {i} outside 0..16")
+        mask |= 1 << int(i)
+    return mask
+
+
+def _mpc_backward(what: str, multi: bool, former_inputs, iterate, seeds, N: int, wrt, status, outputs, workspace):
+    d = Dims(N)
+    B = former_inputs[0].shape[0]
+    dev = former_inputs[0].device
+    ins = _check_batch(former_inputs, d.former_in_nnz, B, what)
+    it = _check_batch(list(iterate), d.solver_in_nnz[6:], B, what + " iterate")
+    sd, M = _seed_struct(seeds, B, N, what, multi)
+    if outputs is not None:
+        wrt = [i for i, t in enumerate(outputs) if t is not None]
+    want = set(range(17)) if wrt is None else {int(i) for i in wrt}
+    mask = _input_mask(want)
+    L = _native.lib()
+    if not multi:  # the QP and all six gradients, whatever is asked for: with nothing asked for, only status is written
+        n = L.srbd_mpc_backward_workspace_doubles(N, B)
+    elif mask == 0:
+        raise ValueError(f"{what}: no former input requested")
+    else:
+        n = L.srbd_mpc_backward_multi_workspace_doubles(N, B, M, mask)
+    outs, outp = _optional_outputs(outputs, d.former_in_nnz, B, dev, what + " outputs", M if multi else None, want)
+    workspace = _workspace(workspace, n, dev, what)
+    rc = L.srbd_mpc_backward_seeds(N, B, M, _native.ptr_array(ins), _native.ptr_array(it), ctypes.byref(sd),
+                                   workspace.data_ptr(), outp, _tensor_ptr(status, torch.int32, B, what, "status"),
+                                   _stream_ptr())
+    _native.check(rc, "srbd_mpc_backward_seeds")
     return outs
 
 
@@ -364,55 +351,21 @@ def mpc_backward(former_inputs: list[torch.Tensor], iterate: list[torch.Tensor],
                  workspace: torch.Tensor | None = None, *, grad_s: torch.Tensor | None = None,
                  grad_z: torch.Tensor | None = None, grad_y: torch.Tensor | None = None,
                  grad_objective: torch.Tensor | None = None):
-    """``srbd_mpc_backward``: qp_former -> pdipm_backward -> qp_former_backward in one call (same bits),
-    from the former inputs, the iterate [x, s, z, y] of the solve and ``grad_x`` -- and, optionally, the
-    cotangents of s, z, y and of the objective (the MPC cost), as ``pdipm_backward``. Returns the gradients of
-    the 17 former inputs (``outputs``: preallocated tensors, None entries are skipped). ``workspace``:
-    float64, srbd_mpc_backward_workspace_doubles(N, B) elements (allocated when None)."""
-    d = Dims(N)
-    B = former_inputs[0].shape[0]
-    dev = former_inputs[0].device
-    seeds = [grad_x, grad_s, grad_z, grad_y, grad_objective]
-    _check_batch(former_inputs, d.former_in_nnz, B, "mpc_backward")
-    _check_batch(list(iterate) + [grad_x], d.solver_in_nnz[6:] + (d.nz,), B, "mpc_backward iterate")
-    outs = _optional_outputs(outputs, d.former_in_nnz, B, dev, "mpc_backward outputs")
-    L = _native.lib()
-    workspace = _workspace(workspace, L.srbd_mpc_backward_workspace_doubles(N, B), dev, "mpc_backward")
-    st = _check_status(status, B, "mpc_backward")
-    if _only_x(seeds):
-        rc = L.srbd_mpc_backward(N, B, _ptrs(former_inputs), _ptrs(iterate), grad_x.data_ptr(), workspace.data_ptr(),
-                                 _ptrs(outs), st, _stream_ptr())
-        _native.check(rc, "srbd_mpc_backward")
-        return outs
-    sd, _ = _seed_struct(seeds, B, N, "mpc_backward", multi=False)
-    rc = L.srbd_mpc_backward_seeds(N, B, 1, _ptrs(former_inputs), _ptrs(iterate), ctypes.byref(sd),
-                                   workspace.data_ptr(), _ptrs(outs), st, _stream_ptr())
-    _native.check(rc, "srbd_mpc_backward_seeds")
-    return outs
+    """qp_former -> pdipm_backward -> qp_former_backward in one call (``srbd_mpc_backward_seeds``; the bits of
+    the three calls), from the former inputs, the iterate [x, s, z, y] of the solve and ``grad_x`` -- and,
+    optionally, the cotangents of s, z, y and of the objective (the MPC cost), as ``pdipm_backward``. Returns
+    the gradients of the 17 former inputs (``outputs``: preallocated tensors, None entries are skipped; with
+    all 17 None only ``status`` is written). ``workspace``: float64,
+    srbd_mpc_backward_workspace_doubles(N, B) elements (allocated when None)."""
+    return _mpc_backward("mpc_backward", False, former_inputs, iterate, [grad_x, grad_s, grad_z, grad_y, grad_objective],
+                         N, None, status, outputs, workspace)
 
 
 # ---- several seeds at one iterate: solution Jacobians and the u0 feedback gain ----
 # The KKT matrix of the adjoint system depends on the QP and the iterate only, so M seeds share one
-# factorisation (srbd_pdipm_backward_multi). Everything below is the derivative of the linearised KKT
-# conditions at the iterate (DESIGN.md 6c): exact at convergence, and at a non-converged iterate the
-# derivative of the Newton step's linear system, as the single-seed entries above.
-
-def _seed_block(grad_x: torch.Tensor, B: int, N: int, what: str):
-    """grad_x (M, 24N), shared by every env, or (B, M, 24N), per env -> (M, the C-ABI's env stride)."""
-    nz = 24 * N
-    if not isinstance(grad_x, torch.Tensor) or not grad_x.is_cuda or grad_x.dtype != torch.float64:
-        raise TypeError(f"{what}: grad_x must be a CUDA float64 tensor")
-    if grad_x.device.index != torch.cuda.current_device():
-        raise ValueError(f"{what}: grad_x is on {grad_x.device}, the current device is cuda:{torch.cuda.current_device()}")
-    if not grad_x.is_contiguous():
-        raise ValueError(f"{what}: grad_x must be contiguous")
-    if grad_x.dim() == 2 and grad_x.shape[1] == nz and grad_x.shape[0] >= 1:
-        return grad_x.shape[0], 0
-    if grad_x.dim() == 3 and grad_x.shape[0] == B and grad_x.shape[2] == nz and grad_x.shape[1] >= 1:
-        return grad_x.shape[1], grad_x.shape[1] * nz
-    raise ValueError(f"{what}: grad_x must be (M, {nz}) (shared by every env) or ({B}, M, {nz}), M >= 1, "
-                     f"got {tuple(grad_x.shape)}")
-
+# factorisation. Everything below is the derivative of the linearised KKT conditions at the iterate
+# (DESIGN.md 6c): exact at convergence, and at a non-converged iterate the derivative of the Newton step's
+# linear system, as the single-seed functions above.
 
 def pdipm_backward_multi(qp: list, iterate: list[torch.Tensor], grad_x: torch.Tensor | None, N: int,
                          status: torch.Tensor | None = None, outputs: list | None = None, *,
@@ -431,28 +384,8 @@ def pdipm_backward_multi(qp: list, iterate: list[torch.Tensor], grad_x: torch.Te
     STATUS_UNSUPPORTED for a QP that is not stage-invariant (all its M rows are NaN), STATUS_NONFINITE
     when the adjoint of any of its seeds is non-finite. The result is the derivative of the linearised
     KKT conditions at the iterate: exact at convergence."""
-    d = Dims(N)
-    B = iterate[0].shape[0]
-    ins = list(qp) + list(iterate)
-    _check_batch(ins, d.solver_in_nnz, B, "pdipm_backward_multi")
-    _require_qp_and_iterate(ins, "pdipm_backward_multi")
-    seeds = [grad_x, grad_s, grad_z, grad_y, grad_objective]
-    if _only_x(seeds):
-        M, stride = _seed_block(grad_x, B, N, "pdipm_backward_multi")
-    else:
-        sd, M = _seed_struct(seeds, B, N, "pdipm_backward_multi", multi=True)
-        if grad_objective is not None and ins[3] is None:
-            raise ValueError("pdipm_backward_multi: grad_objective needs f (qp[3])")
-    outs = _optional_outputs(outputs, d.former_out_nnz, B, iterate[0].device, "pdipm_backward_multi outputs", M)
-    st = _check_status(status, B, "pdipm_backward_multi")
-    if _only_x(seeds):
-        rc = _native.lib().srbd_pdipm_backward_multi(N, B, M, _ptrs(ins), grad_x.data_ptr(), stride, _ptrs(outs), st,
-                                                     _stream_ptr())
-        _native.check(rc, "srbd_pdipm_backward_multi")
-        return outs
-    rc = _native.lib().srbd_pdipm_backward_seeds(N, B, M, _ptrs(ins), ctypes.byref(sd), _ptrs(outs), st, _stream_ptr())
-    _native.check(rc, "srbd_pdipm_backward_seeds")
-    return outs
+    return _pdipm_backward("pdipm_backward_multi", True, qp, iterate,
+                           [grad_x, grad_s, grad_z, grad_y, grad_objective], N, status, outputs)
 
 
 def qp_former_backward_multi(former_inputs: list[torch.Tensor], qp_grads: list, N: int, outputs: list | None = None):
@@ -460,32 +393,23 @@ def qp_former_backward_multi(former_inputs: list[torch.Tensor], qp_grads: list, 
     gradient, at least one given) -> the gradients of the 17 former inputs, each (B, M, width); row
     [b, k] uses env b's former inputs and has the bits of the single-seed call on that row.
     ``outputs``: preallocated tensors, None entries are skipped."""
+    what = "qp_former_backward_multi"
     d = Dims(N)
     B = former_inputs[0].shape[0]
-    _check_batch(former_inputs, d.former_in_nnz, B, "qp_former_backward_multi")
+    ins = _check_batch(former_inputs, d.former_in_nnz, B, what)
     given = [(g, w) for g, w in zip(qp_grads, d.former_out_nnz) if g is not None]
     if not given:
-        raise ValueError("qp_former_backward_multi: at least one QP gradient is needed (it carries the seed count)")
+        raise ValueError(f"{what}: at least one QP gradient is needed (it carries the seed count)")
     g0, w0 = given[0]
     if g0.dim() != 3 or g0.shape[0] != B or g0.shape[2] != w0 or g0.shape[1] < 1:
-        raise ValueError(f"qp_former_backward_multi: gradients must be ({B}, M, width), got {tuple(g0.shape)}")
+        raise ValueError(f"{what}: gradients must be ({B}, M, width), got {tuple(g0.shape)}")
     M = g0.shape[1]
-    _check_batch(qp_grads, [M * w for w in d.former_out_nnz], B, "qp_former_backward_multi gradients")
-    outs = _optional_outputs(outputs, d.former_in_nnz, B, former_inputs[0].device, "qp_former_backward_multi outputs",
-                             M)
-    rc = _native.lib().srbd_qp_former_backward_multi(N, B, M, _ptrs(former_inputs), _ptrs(qp_grads), _ptrs(outs),
+    grads = _check_batch(qp_grads, [M * w for w in d.former_out_nnz], B, what + " gradients")
+    outs, outp = _optional_outputs(outputs, d.former_in_nnz, B, former_inputs[0].device, what + " outputs", M)
+    rc = _native.lib().srbd_qp_former_backward_multi(N, B, M, _native.ptr_array(ins), _native.ptr_array(grads), outp,
                                                      _stream_ptr())
     _native.check(rc, "srbd_qp_former_backward_multi")
     return outs
-
-
-def _input_mask(wrt) -> int:
-    mask = 0
-    for i in wrt:
-        if not 0 <= int(i) < 17:
-            raise ValueError(f"wrt: former-input index {i} outside 0..16")
-        mask |= 1 << int(i)
-    return mask
 
 
 def mpc_backward_multi(former_inputs: list[torch.Tensor], iterate: list[torch.Tensor], grad_x: torch.Tensor | None,
@@ -493,46 +417,19 @@ def mpc_backward_multi(former_inputs: list[torch.Tensor], iterate: list[torch.Te
                        workspace: torch.Tensor | None = None, *, grad_s: torch.Tensor | None = None,
                        grad_z: torch.Tensor | None = None, grad_y: torch.Tensor | None = None,
                        grad_objective: torch.Tensor | None = None):
-    """``srbd_mpc_backward_multi``: qp_former (once per env) -> pdipm_backward_multi -> qp_former_backward_multi
-    in one call (same bits), for the M seeds ``grad_x`` ((M, 24N) shared, or (B, M, 24N)).
+    """qp_former (once per env) -> pdipm_backward_multi -> qp_former_backward_multi in one call
+    (``srbd_mpc_backward_seeds``; the bits of the three calls), for the M seeds ``grad_x`` ((M, 24N) shared,
+    or (B, M, 24N)).
 
-    ``wrt``: the former-input indices wanted (None: all 17). Returns a list of 17 with (B, M, width)
-    gradients at those indices and None elsewhere: the others are neither computed nor allocated, and
-    only the QP gradients the wanted inputs read are held in the workspace
+    ``wrt``: the former-input indices wanted (None: all 17; at least one). Returns a list of 17 with
+    (B, M, width) gradients at those indices and None elsewhere: the others are neither computed nor
+    allocated, and only the QP gradients the wanted inputs read are held in the workspace
     (``srbd_mpc_backward_multi_workspace_doubles``). ``outputs``: preallocated tensors instead (None
     entries are skipped; ``wrt`` is then taken from it). ``grad_s``, ``grad_z``, ``grad_y``,
     ``grad_objective``: cotangents of the solve's other outputs, as ``pdipm_backward_multi``. The result is
     the derivative of the linearised KKT conditions at the iterate: exact at convergence."""
-    d = Dims(N)
-    B = former_inputs[0].shape[0]
-    dev = former_inputs[0].device
-    _check_batch(former_inputs, d.former_in_nnz, B, "mpc_backward_multi")
-    _check_batch(list(iterate), d.solver_in_nnz[6:], B, "mpc_backward_multi iterate")
-    seeds = [grad_x, grad_s, grad_z, grad_y, grad_objective]
-    if _only_x(seeds):
-        M, stride = _seed_block(grad_x, B, N, "mpc_backward_multi")
-    else:
-        sd, M = _seed_struct(seeds, B, N, "mpc_backward_multi", multi=True)
-    if outputs is not None:
-        wrt = [i for i, t in enumerate(outputs) if t is not None]
-    want = set(range(17)) if wrt is None else {int(i) for i in wrt}
-    mask = _input_mask(want)
-    if mask == 0:
-        raise ValueError("mpc_backward_multi: no former input requested")
-    outs = _optional_outputs(outputs, d.former_in_nnz, B, dev, "mpc_backward_multi outputs", M, want)
-    L = _native.lib()
-    workspace = _workspace(workspace, L.srbd_mpc_backward_multi_workspace_doubles(N, B, M, mask), dev,
-                           "mpc_backward_multi")
-    st = _check_status(status, B, "mpc_backward_multi")
-    if _only_x(seeds):
-        rc = L.srbd_mpc_backward_multi(N, B, M, _ptrs(former_inputs), _ptrs(iterate), grad_x.data_ptr(), stride,
-                                       workspace.data_ptr(), _ptrs(outs), st, _stream_ptr())
-        _native.check(rc, "srbd_mpc_backward_multi")
-        return outs
-    rc = L.srbd_mpc_backward_seeds(N, B, M, _ptrs(former_inputs), _ptrs(iterate), ctypes.byref(sd),
-                                   workspace.data_ptr(), _ptrs(outs), st, _stream_ptr())
-    _native.check(rc, "srbd_mpc_backward_seeds")
-    return outs
+    return _mpc_backward("mpc_backward_multi", True, former_inputs, iterate,
+                         [grad_x, grad_s, grad_z, grad_y, grad_objective], N, wrt, status, outputs, workspace)
 
 
 def unit_seeds(N: int, rows, device="cuda", of: str = "x") -> torch.Tensor:
@@ -591,36 +488,10 @@ def mpc_feedback_gain(former_inputs: list[torch.Tensor], iterate: list[torch.Ten
                         outputs=outs, workspace=workspace)[0]
 
 
-class _MPCSolveFunction(torch.autograd.Function):
-    """x = mpc_solve(former_inputs): forward ``srbd_mpc_solve_fused``, backward ``srbd_mpc_backward`` on the
-    saved iterate (the adjoint KKT solve and the former's vector-Jacobian product)."""
-
-    @staticmethod
-    def forward(ctx, N, n_iter, y0, *former_inputs):
-        ins = [t.detach().contiguous() for t in former_inputs]
-        x, s, z, y = mpc_solve(ins, N, n_iter, y0)[:4]
-        ctx.N = N
-        ctx.shapes = [t.shape for t in former_inputs]
-        ctx.save_for_backward(*ins, x, s, z, y)
-        return x.clone()  # the saved x stays what the backward pass linearises at
-
-    @staticmethod
-    def backward(ctx, grad_x):
-        saved = ctx.saved_tensors
-        ins, iterate = list(saved[:17]), list(saved[17:])
-        d = Dims(ctx.N)
-        B = ins[0].shape[0]
-        need = ctx.needs_input_grad[3:]
-        outs = [torch.empty((B, w), dtype=torch.float64, device=grad_x.device) if n else None
-                for w, n in zip(d.former_in_nnz, need)]
-        mpc_backward(ins, iterate, grad_x.contiguous(), ctx.N, outputs=outs)
-        return (None, None, None) + tuple(o.view(s) if o is not None else None for o, s in zip(outs, ctx.shapes))
-
-
 class _MPCSolveOutputsFunction(torch.autograd.Function):
-    """The named outputs of mpc_solve(former_inputs), among x, s, z, y and the objective: forward ``srbd_mpc_solve_fused`` (``_info`` for the objective),
-    backward ``srbd_mpc_backward`` / ``srbd_mpc_backward_seeds`` on the saved iterate (the adjoint KKT solve and
-    the former's vector-Jacobian product) with whichever cotangents autograd supplies."""
+    """The named outputs of mpc_solve(former_inputs), among x, s, z, y and the objective: forward ``mpc_solve``,
+    backward ``mpc_backward`` on the saved iterate (the adjoint KKT solve and the former's vector-Jacobian
+    product) with whichever cotangents autograd supplies."""
 
     @staticmethod
     def forward(ctx, N, n_iter, y0, outputs, *former_inputs):
@@ -667,24 +538,11 @@ def mpc_solve_autograd(former_inputs: list[torch.Tensor], N: int, n_iter: int, y
     outputs = tuple(outputs)
     if not outputs or len(set(outputs)) != len(outputs) or any(k not in _native.SEED_KINDS for k in outputs):
         raise ValueError(f"mpc_solve_autograd: outputs must be distinct names out of {', '.join(_native.SEED_KINDS)}")
-    if outputs == ("x",):
-        return _MPCSolveFunction.apply(N, n_iter, float(y0), *former_inputs)
-    return _MPCSolveOutputsFunction.apply(N, n_iter, float(y0), outputs, *former_inputs)
+    res = _MPCSolveOutputsFunction.apply(N, n_iter, float(y0), outputs, *former_inputs)
+    return res[0] if outputs == ("x",) else res
 
 
 # ---- backward pass of the controller step's FP32 ends (include/srbd_mpc.h: wrench cotangent -> FP32 inputs) ----
-
-def _f32_arg(t, shape, what: str, name: str):
-    """None, or a contiguous float32 CUDA tensor of `shape` on the current device -> its pointer."""
-    if t is None:
-        return None
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-        raise TypeError(f"{what}: {name} must be a CUDA float32 tensor")
-    if tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device.index != torch.cuda.current_device():
-        raise ValueError(f"{what}: {name} must be a contiguous {tuple(shape)} tensor on the current device, "
-                         f"got {tuple(t.shape)} on {t.device}")
-    return t.data_ptr()
-
 
 def _torque_cotangent(B: int, grad_tau, contact_jacobian, contact_bool, what: str):
     """(ndof, J pointer, contact pointer, grad_tau pointer) of the optional stance-torque cotangent."""
@@ -695,8 +553,9 @@ def _torque_cotangent(B: int, grad_tau, contact_jacobian, contact_bool, what: st
     if grad_tau.dim() != 3 or grad_tau.shape[2] < 1:
         raise ValueError(f"{what}: grad_tau must be ({B}, 2, ndof)")
     ndof = grad_tau.shape[2]
-    return (ndof, _f32_arg(contact_jacobian, (B, 2, 6, ndof), what, "contact_jacobian"),
-            _f32_arg(contact_bool, (B, 2), what, "contact_bool"), _f32_arg(grad_tau, (B, 2, ndof), what, "grad_tau"))
+    return (ndof, _tensor_ptr(contact_jacobian, torch.float32, (B, 2, 6, ndof), what, "contact_jacobian"),
+            _tensor_ptr(contact_bool, torch.float32, (B, 2), what, "contact_bool"),
+            _tensor_ptr(grad_tau, torch.float32, (B, 2, ndof), what, "grad_tau"))
 
 
 def u0_wrench_backward(x: torch.Tensor, rotation_body: torch.Tensor, grad_wrench: torch.Tensor, N: int,
@@ -711,16 +570,16 @@ def u0_wrench_backward(x: torch.Tensor, rotation_body: torch.Tensor, grad_wrench
     ``want_rotation``)."""
     what = "u0_wrench_backward"
     B = x.shape[0]
-    _check_batch([x], [24 * N], B, what)
     if grad_x is None:
         grad_x = torch.empty((B, 24 * N), dtype=torch.float64, device=x.device)
-    _check_batch([grad_x], [24 * N], B, what + " grad_x")
     gR = torch.empty((B, 9), dtype=torch.float64, device=x.device) if want_rotation else None
     ndof, J, cb, gt = _torque_cotangent(B, grad_tau, contact_jacobian, contact_bool, what)
     rc = _native.lib().srbd_u0_wrench_backward(
-        N, B, x.data_ptr(), _f32_arg(rotation_body, (B, 3, 3), what, "rotation_body"),
-        _f32_arg(grad_wrench, (B, 2, 6), what, "grad_wrench"), ndof, J, cb, gt, grad_x.data_ptr(),
-        None if gR is None else gR.data_ptr(), _stream_ptr())
+        N, B, _tensor_ptr(x, torch.float64, B * 24 * N, what, "x"),
+        _tensor_ptr(rotation_body, torch.float32, (B, 3, 3), what, "rotation_body"),
+        _tensor_ptr(grad_wrench, torch.float32, (B, 2, 6), what, "grad_wrench"), ndof, J, cb, gt,
+        _tensor_ptr(grad_x, torch.float64, B * 24 * N, what, "grad_x"), None if gR is None else gR.data_ptr(),
+        _stream_ptr())
     _native.check(rc, "srbd_u0_wrench_backward")
     return grad_x, gR
 
@@ -745,16 +604,16 @@ def prepare_inputs_backward(prep, input_grads: list, N: int, B: int, wrt, grad_w
     """``srbd_prepare_inputs_backward``: the 17 FP64 former-input cotangents (None: zero) -> float32 gradients of
     the controller tensors named in ``wrt`` (``_native.PREP_GRAD_NAMES``), as a dict. ``prep``: the
     ``_native.MPCPrep`` of the step, its ``first_run`` the flag before the step."""
-    import ctypes
     what = "prepare_inputs_backward"
-    _check_batch(input_grads, Dims(N).former_in_nnz, B, what)
-    _check_batch([grad_rotation_body_direct], [9], B, what + " grad_rotation_body_direct")
+    grads = _check_batch(input_grads, Dims(N).former_in_nnz, B, what)
     device = torch.device("cuda", torch.cuda.current_device())
     out, ptrs, _ = _prep_grad_outputs(B, N, wrt, device, what)
     rc = _native.lib().srbd_prepare_inputs_backward(
-        N, B, ctypes.byref(prep), _ptrs(input_grads), _f32_arg(grad_wpd_out, (B, 3), what, "grad_wpd_out"),
-        _f32_arg(grad_yaw_out, (B,), what, "grad_yaw_out"),
-        None if grad_rotation_body_direct is None else grad_rotation_body_direct.data_ptr(), ptrs, _stream_ptr())
+        N, B, ctypes.byref(prep), _native.ptr_array(grads),
+        _tensor_ptr(grad_wpd_out, torch.float32, (B, 3), what, "grad_wpd_out"),
+        _tensor_ptr(grad_yaw_out, torch.float32, (B,), what, "grad_yaw_out"),
+        _tensor_ptr(grad_rotation_body_direct, torch.float64, B * 9, what, "grad_rotation_body_direct"), ptrs,
+        _stream_ptr())
     _native.check(rc, "srbd_prepare_inputs_backward")
     return out
 
@@ -774,28 +633,21 @@ def mpc_step_backward(prep, former_inputs: list[torch.Tensor], iterate: list[tor
     d = Dims(N)
     B = former_inputs[0].shape[0]
     dev = former_inputs[0].device
-    _check_batch(former_inputs, d.former_in_nnz, B, what)
-    _check_batch(list(iterate), d.solver_in_nnz[6:], B, what + " iterate")
+    ins = _check_batch(former_inputs, d.former_in_nnz, B, what)
+    it = _check_batch(list(iterate), d.solver_in_nnz[6:], B, what + " iterate")
     if grad_wrench is None and grad_cost is None:
         raise ValueError(f"{what}: grad_wrench and grad_cost are both None")
     out, ptrs, mask = _prep_grad_outputs(B, N, wrt, dev, what)
     L = _native.lib()
     ndof, J, cb, gt = _torque_cotangent(B, grad_tau, contact_jacobian, contact_bool, what)
-    if grad_cost is not None:
-        workspace = _workspace(workspace, L.srbd_mpc_step_backward_cost_workspace_doubles(N, B, mask), dev, what)
-        rc = L.srbd_mpc_step_backward_cost(
-            N, B, ctypes.byref(prep), _ptrs(former_inputs), _ptrs(iterate),
-            _f32_arg(grad_wrench, (B, 2, 6), what, "grad_wrench"), _f32_arg(grad_cost, (B,), what, "grad_cost"),
-            ndof, J, cb, gt, _f32_arg(grad_wpd_out, (B, 3), what, "grad_wpd_out"),
-            _f32_arg(grad_yaw_out, (B,), what, "grad_yaw_out"), workspace.data_ptr(), ptrs,
-            _check_status(status, B, what), _stream_ptr())
-        _native.check(rc, "srbd_mpc_step_backward_cost")
-        return out
-    workspace = _workspace(workspace, L.srbd_mpc_step_backward_workspace_doubles(N, B, mask), dev, what)
-    rc = L.srbd_mpc_step_backward(
-        N, B, ctypes.byref(prep), _ptrs(former_inputs), _ptrs(iterate),
-        _f32_arg(grad_wrench, (B, 2, 6), what, "grad_wrench"), ndof, J, cb, gt,
-        _f32_arg(grad_wpd_out, (B, 3), what, "grad_wpd_out"), _f32_arg(grad_yaw_out, (B,), what, "grad_yaw_out"),
-        workspace.data_ptr(), ptrs, _check_status(status, B, what), _stream_ptr())
-    _native.check(rc, "srbd_mpc_step_backward")
+    entry = "srbd_mpc_step_backward_cost" if grad_cost is not None else "srbd_mpc_step_backward"
+    workspace = _workspace(workspace, getattr(L, entry + "_workspace_doubles")(N, B, mask), dev, what)
+    args = [N, B, ctypes.byref(prep), _native.ptr_array(ins), _native.ptr_array(it),
+            _tensor_ptr(grad_wrench, torch.float32, (B, 2, 6), what, "grad_wrench"), ndof, J, cb, gt,
+            _tensor_ptr(grad_wpd_out, torch.float32, (B, 3), what, "grad_wpd_out"),
+            _tensor_ptr(grad_yaw_out, torch.float32, (B,), what, "grad_yaw_out"), workspace.data_ptr(), ptrs,
+            _tensor_ptr(status, torch.int32, B, what, "status"), _stream_ptr()]
+    if grad_cost is not None:  # the _cost entry takes grad_cost after grad_wrench
+        args.insert(6, _tensor_ptr(grad_cost, torch.float32, (B,), what, "grad_cost"))
+    _native.check(getattr(L, entry)(*args), entry)
     return out

@@ -145,19 +145,20 @@ def test_autograd_inputs_without_requires_grad_get_none():
     torch.cuda.synchronize()
     assert ins[15].grad is not None and torch.isfinite(ins[15].grad).all() and ins[15].grad.abs().max() > 0
     assert all(ins[i].grad is None for i in range(17) if i != 15)
-    # the Function itself hands None to every input that did not ask (and to N, n_iter, y0)
+    # the Function itself hands None to every input that did not ask (and to N, n_iter, y0, outputs)
 
     class Ctx:
         N = 3
-        needs_input_grad = (False,) * 3 + tuple(i == 15 for i in range(17))
+        outputs = ("x",)
+        needs_input_grad = (False,) * 4 + tuple(i == 15 for i in range(17))
         shapes = [t.shape for t in ins]
         saved_tensors = tuple(t.detach() for t in ins) + tuple(solver.mpc_solve([t.detach() for t in ins], N, K)[:4])
-    outs = solver._MPCSolveFunction.backward(Ctx, torch.ones_like(x))
+    outs = solver._MPCSolveOutputsFunction.backward(Ctx, torch.ones_like(x))
     torch.cuda.synchronize()
-    assert len(outs) == 20 and all(o is None for j, o in enumerate(outs) if j != 18)
+    assert len(outs) == 21 and all(o is None for j, o in enumerate(outs) if j != 19)
     g = torch.zeros_like(x)
     g[:, 12 * N:12 * N + 12] = 1.0
-    assert torch.equal(solver._MPCSolveFunction.backward(Ctx, g)[18], ins[15].grad)
+    assert torch.equal(solver._MPCSolveOutputsFunction.backward(Ctx, g)[19], ins[15].grad)
 
 
 # ---- 5. determinism -------------------------------------------------------------------------------

@@ -78,6 +78,24 @@ def _seeds_entry(qp, it, N, M, shared, seeds: dict, status=None):
     return outs
 
 
+def _x_only_entry(qp, it, N, M, grad_x, status=None):
+    """srbd_pdipm_backward itself (M None: grad_x (B, 24N), outputs (B, width)) or srbd_pdipm_backward_multi
+    (grad_x (M, 24N), shared, or (B, M, 24N); outputs (B, M, width)): the Python wrappers call neither."""
+    L = _native.lib()
+    B = it[0].shape[0]
+    outs = [torch.full((B, w) if M is None else (B, M, w), float("nan"), dtype=torch.float64, device="cuda")
+            for w in layout.Dims(N).former_out_nnz]
+    ins, st = solver._ptrs(list(qp) + list(it)), None if status is None else status.data_ptr()
+    if M is None:
+        rc = L.srbd_pdipm_backward(N, B, ins, grad_x.data_ptr(), solver._ptrs(outs), st, solver._stream_ptr())
+    else:
+        stride = 0 if grad_x.dim() == 2 else M * 24 * N
+        rc = L.srbd_pdipm_backward_multi(N, B, M, ins, grad_x.data_ptr(), stride, solver._ptrs(outs), st,
+                                         solver._stream_ptr())
+    _native.check(rc, "srbd_pdipm_backward" if M is None else "srbd_pdipm_backward_multi")
+    return outs
+
+
 # ---- 1. the x-only entries keep their bits --------------------------------------------------------
 
 @pytest.mark.parametrize("N", C.HORIZONS)
@@ -85,13 +103,13 @@ def test_x_only_entries_equal_the_seeds_entry_with_grad_x_alone(N):
     _, qp, it = _dev_case(N, "random", 5)
     g = _dev_seeds(N)["x"]
     st_old, st_new = _status(), _status()
-    old = solver.pdipm_backward(qp, it, g, N, status=st_old)
+    old = _x_only_entry(qp, it, N, None, g, st_old)
     new = _seeds_entry(qp, it, N, 1, False, {"x": g}, st_new)
     block = torch.stack([g, g.flip(0), g], dim=1).contiguous()  # M = 3, per env
-    old_m = solver.pdipm_backward_multi(qp, it, block, N)
+    old_m = _x_only_entry(qp, it, N, 3, block)
     new_m = _seeds_entry(qp, it, N, 3, False, {"x": block})
     shared = g[:2].contiguous()  # M = 2, shared by every env
-    old_s = solver.pdipm_backward_multi(qp, it, shared, N)
+    old_s = _x_only_entry(qp, it, N, 2, shared)
     new_s = _seeds_entry(qp, it, N, 2, True, {"x": shared})
     # grad_x alone runs the kernels' x-only instantiation; all-zero tensors for the rest run the full one
     sd = _dev_seeds(N)

@@ -14,15 +14,21 @@ from biped_pympc_amd import _native, build
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _declared_functions():
-    names = set()
+def _declarations():
+    """name -> parameter count of every function include/*.h declares ((void): 0)."""
+    decls = {}
     for h in glob.glob(os.path.join(ROOT, "include", "*.h")):
         src = open(h).read()
         src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-        for m in re.finditer(r"^\s*[A-Za-z_][\w\s\*]*?\b([A-Za-z_]\w*)\s*\(", src, flags=re.M):
+        for m in re.finditer(r"^\s*[A-Za-z_][\w\s\*]*?\b([A-Za-z_]\w*)\s*\(([^()]*)\)", src, flags=re.M):
             if m.group(1) not in ("if", "defined"):
-                names.add(m.group(1))
-    return names
+                params = m.group(2).strip()
+                decls[m.group(1)] = 0 if params in ("", "void") else params.count(",") + 1
+    return decls
+
+
+def _declared_functions():
+    return set(_declarations())
 
 
 def _exports(path):
@@ -42,6 +48,28 @@ def test_core_library_exports_every_declared_symbol():
     exports = _exports(_native.lib_path())
     missing = (_declared_functions() - {"evaluate"}) - exports
     assert not missing, missing
+
+
+def test_every_bound_signature_is_exported():
+    build.build()
+    missing = set(_native.SIGNATURES) - _exports(_native.lib_path())
+    assert not missing, missing
+
+
+def test_bound_signatures_have_the_header_parameter_counts():
+    decls = _declarations()
+    assert decls["srbd_abi_version"] == 0 and decls["srbd_mpc_step_backward_cost"] == 17  # the regex reads the lists
+    wrong = {name: (len(argtypes), decls.get(name)) for name, (_, argtypes) in _native.SIGNATURES.items()
+             if decls.get(name) != len(argtypes)}
+    assert not wrong, wrong
+
+
+def test_every_declared_function_is_bound_or_listed():
+    not_bound_from_python = ()  # srbd_* entries that are for C callers only: none so far
+    declared = {n for n in _declarations() if n.startswith("srbd_")}
+    assert len(declared) > 50 and set(not_bound_from_python) <= declared
+    unbound = declared - set(_native.SIGNATURES) - set(not_bound_from_python)
+    assert not unbound, unbound
 
 
 @pytest.mark.parametrize("fn,N,K", build.DROPIN_CONFIGS)
