@@ -297,6 +297,36 @@ def build_prim_harness(force: bool = False, verbose: bool = False) -> str:
     return PRIM_HARNESS_LIB
 
 
+# ---- test-only harness of the column-split chain primitives (tests/csrc/prim_harness_split.hip ->
+# tests/libprim_harness_split.so, loaded by tests/test_gpu_primitives_split.py): the same recipe ----
+PRIM_SPLIT_SRC = os.path.join(ROOT, "tests", "csrc", "prim_harness_split.hip")
+PRIM_SPLIT_LIB = os.path.join(ROOT, "tests", "libprim_harness_split.so")
+
+
+def prim_harness_split_hash() -> str:
+    parts = [ARCH, repr(_COMMON_FLAGS), "prim_harness_split.hip", open(PRIM_SPLIT_SRC, "rb").read()]
+    for f in sorted(os.listdir(CSRC)):
+        if f.endswith(".hpp"):
+            parts += [f, open(os.path.join(CSRC, f), "rb").read()]
+    return _digest(parts)
+
+
+def build_prim_harness_split(force: bool = False, verbose: bool = False) -> str:
+    pid = prim_harness_split_hash()
+    if force or prim_harness_embedded_id(PRIM_SPLIT_LIB) != pid:
+        tmp = PRIM_SPLIT_LIB + ".tmp"
+        cmd = [HIPCC, f"--offload-arch={ARCH}", *_COMMON_FLAGS, f"-I{CSRC}", "-fPIC", "-shared",
+               f'-DSRBD_PRIM_ID="{pid}"', "-o", tmp, PRIM_SPLIT_SRC]
+        if verbose:
+            print(" ".join(cmd))
+        _run(cmd)
+        os.replace(tmp, PRIM_SPLIT_LIB)
+        if prim_harness_embedded_id(PRIM_SPLIT_LIB) != pid:
+            raise RuntimeError(f"{PRIM_SPLIT_LIB}: id {prim_harness_embedded_id(PRIM_SPLIT_LIB)} != source hash {pid}")
+    return PRIM_SPLIT_LIB
+
+
 if __name__ == "__main__":
     print(build(force=True, verbose=True))
     print(build_prim_harness(force=True, verbose=True))
+    print(build_prim_harness_split(force=True, verbose=True))

@@ -242,4 +242,129 @@ __device__ __forceinline__ void inverse_rows12(double (&Sr)[12], double (&Dr)[12
   for (int j = 0; j < 12; ++j) Dr[j] = Sr[j] * nsc;
 }
 
+// ---- the same primitives with a 12x12 block split by column across the two halves of the wave ----
+// Half A (lanes 0..31: DPP rows 0 and 1, the two twisted groups) holds columns {0,1,2,6,7,8} of its
+// row, half B (lanes 32..63: DPP rows 2 and 3) columns {3,4,5,9,10,11}: slot j of half h is column
+// split_col(h, j), row r = lane & 15 as before, so lanes i and i + 32 together hold one row. Every
+// per-lane loop over a row is then 6 long instead of 12. A broadcast-FMA names ONE source lane for the
+// whole wave, so wherever the two halves need different rows' values, half B keeps them three lanes
+// down (lane split_col(0, j) holds what belongs to row split_col(1, j): shl3_b).
+__host__ __device__ constexpr int split_col(int h, int j) { return (j < 3 ? j : j + 3) + 3 * h; }
+
+// v of half A and of half B (lane i & 31 of each), in every lane of both halves: one copy and one
+// v_permlane32_swap_b32 per dword (the swap exchanges lanes 32..63 of its first operand with lanes
+// 0..31 of its second; with both holding v, the first ends as A's value everywhere, the second B's).
+// The builtin stays outside the asm blocks so that the hazard recognizer sees it.
+__device__ __forceinline__ void cross_halves(double v, double& a, double& b) {
+  const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
+  const auto l = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+  const auto h = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+  a = __hiloint2double((int)h[0], (int)l[0]);
+  b = __hiloint2double((int)h[1], (int)l[1]);
+}
+// half B: lane i of every 16-lane row <- lane i + 3 (lanes 0,1,2,6,7,8 fetch rows 3,4,5,9,10,11);
+// half A unchanged (row_mask 0xC: DPP rows 2 and 3 only)
+__device__ __forceinline__ double shl3_b(double v) { return __builtin_amdgcn_update_dpp(v, v, 0x103, 0xC, 0xF, false); }
+
+// exec &= (lo, hi) for the instructions INS of one asm block (32-bit literals: a 64-bit SALU operand
+// takes no 64-bit literal)
+#define SRBD_EXEC_AND "s_and_b32 exec_lo, exec_lo, %[ml]\n\ts_and_b32 exec_hi, exec_hi, %[mh]\n\t"
+template <int K>
+struct SplitPivot {
+  static constexpr int H = (K % 6) >= 3;            // the half that holds column K ...
+  static constexpr int J = K % 3 + (K >= 6 ? 3 : 0);  // ... in this slot
+  static_assert(split_col(H, J) == K, "slot of column K");
+  static constexpr uint32_t m16 = (1u << K) | (K == 11 ? 0xF000u : 0u), m32 = m16 | (m16 << 16);
+  static constexpr uint32_t lo = H ? 0u : m32, hi = H ? m32 : 0u;        // pivot lanes of the owning half
+  static constexpr uint32_t hlo = H ? 0u : ~0u, hhi = H ? ~0u : 0u;      // the owning half
+};
+#define SRBD_FMAC6(K)                                                                              \
+  SRBD_FMAC_BC("%0", "%0", "-%6", K) SRBD_FMAC_BC("%1", "%1", "-%6", K) SRBD_FMAC_BC("%2", "%2", "-%6", K) \
+  SRBD_FMAC_BC("%3", "%3", "-%6", K) SRBD_FMAC_BC("%4", "%4", "-%6", K) SRBD_FMAC_BC("%5", "%5", "-%6", K)
+#define SRBD_PIVOT6_CASE(K)                                                                        \
+  case K:                                                                                          \
+    asm("s_nop 1\n" SRBD_FMAC6(K) SRBD_ASM_TAIL                                                     \
+        : "+v"(S[0]), "+v"(S[1]), "+v"(S[2]), "+v"(S[3]), "+v"(S[4]), "+v"(S[5])                  \
+        : "v"(t));                                                                                 \
+    break;
+// S[j] -= S[j](lane k) * t for the six slots of this half (the owning half's slot of column k takes a
+// harmless update: the caller overwrites it)
+__device__ __forceinline__ void pivot_update6(double (&S)[6], double t, int k) {
+  switch (k) {
+    SRBD_PIVOT6_CASE(0) SRBD_PIVOT6_CASE(1) SRBD_PIVOT6_CASE(2) SRBD_PIVOT6_CASE(3)
+    SRBD_PIVOT6_CASE(4) SRBD_PIVOT6_CASE(5) SRBD_PIVOT6_CASE(6) SRBD_PIVOT6_CASE(7)
+    SRBD_PIVOT6_CASE(8) SRBD_PIVOT6_CASE(9) SRBD_PIVOT6_CASE(10)
+    default: asm("s_nop 1\n" SRBD_FMAC6(11) SRBD_ASM_TAIL
+                 : "+v"(S[0]), "+v"(S[1]), "+v"(S[2]), "+v"(S[3]), "+v"(S[4]), "+v"(S[5])
+                 : "v"(t));
+  }
+}
+// Pivot K of gj_pivot on the split block: the owning half forms pk, id and t as gj_pivot does; the
+// other half's own t comes from the wrong column (it may be inf or NaN) and is replaced by the owning
+// half's before anything uses it. Every element then sees the FMA sequence of gj_pivot: the same bits.
+template <int K>
+__device__ __forceinline__ void gj_pivot_split(double (&Sr)[6], double& sc) {
+  using P = SplitPivot<K>;
+  const double pk = bc16(Sr[P::J], K);
+  uint64_t sv;
+  asm("s_mov_b64 %[sv], exec\n\t" SRBD_EXEC_AND "v_mov_b64 %[x], 0\n\ts_mov_b64 exec, %[sv]"
+      : [x] "+v"(Sr[P::J]), [sv] "=&s"(sv)
+      : [ml] "n"(P::lo), [mh] "n"(P::hi)
+      : "scc");
+  const double id = rcp3(pk);
+  double ta, tb;
+  cross_halves(Sr[P::J] * id, ta, tb);
+  const double t = P::H ? tb : ta;  // 0 on the pivot lanes of both halves
+  pivot_update6(Sr, t, K);
+  // owning half: a_rK <- t; its pivot lanes: a_KK <- -1, scale <- id
+  asm("s_mov_b64 %[sv], exec\n\t"
+      "s_and_b32 exec_lo, exec_lo, %[hl]\n\ts_and_b32 exec_hi, exec_hi, %[hh]\n\tv_mov_b64 %[x], %[t]\n\t"
+      SRBD_EXEC_AND "v_mov_b64 %[x], -1.0\n\tv_mov_b64 %[s], %[id]\n\ts_mov_b64 exec, %[sv]"
+      : [x] "+v"(Sr[P::J]), [s] "+v"(sc), [sv] "=&s"(sv)
+      : [t] "v"(t), [id] "v"(id), [hl] "n"(P::hlo), [hh] "n"(P::hhi), [ml] "n"(P::lo), [mh] "n"(P::hi)
+      : "scc");
+  if constexpr (K < 11) gj_pivot_split<K + 1>(Sr, sc);
+}
+// inverse_rows12<false> on the split block: on exit Dr[j] = (A^-1)_{r, split_col(h, j)}, bit for bit
+// what inverse_rows12 leaves in Dr[split_col(h, j)]. Both halves of a group must be active. A row's
+// scale is set in the half that holds its diagonal element (0 in the other) and crosses once.
+__device__ __forceinline__ void inverse_rows12_split(double (&Sr)[6], double (&Dr)[6]) {
+  double sc = 0.0;
+  gj_pivot_split<0>(Sr, sc);
+  double sa, sb;
+  cross_halves(sc, sa, sb);
+  const double nsc = -(sa + sb);  // one of the two is the scale, the other 0
+#pragma unroll
+  for (int j = 0; j < 6; ++j) Dr[j] = Sr[j] * nsc;
+}
+
+// dot_bc12 on the split block: c[j] = the row's element of column split_col(h, j), v one element per
+// row (the same in both halves). Each half sums its six terms; the halves' partial sums cross and are
+// added, pA + pB in both halves: the same bits in lanes i and i + 32 (a 12-term sum reassociated
+// against dot_bc12: the one place where the split changes bits).
+#define SRBD_DOT6(NEG)                                                                                 \
+  asm("s_nop 1\n"                                                                                      \
+      SRBD_FMAC_BC("%0", "%3", NEG "%4", 0) SRBD_FMAC_BC("%1", "%3", NEG "%5", 1) SRBD_FMAC_BC("%2", "%3", NEG "%6", 2) \
+      SRBD_FMAC_BC("%0", "%3", NEG "%7", 6) SRBD_FMAC_BC("%1", "%3", NEG "%8", 7) SRBD_FMAC_BC("%2", "%3", NEG "%9", 8) \
+      SRBD_ASM_TAIL                                                                                    \
+      : "+v"(a0), "+v"(a1), "+v"(a2)                                                                   \
+      : "v"(vs), "v"(c[0]), "v"(c[1]), "v"(c[2]), "v"(c[3]), "v"(c[4]), "v"(c[5]))
+__device__ __forceinline__ double dot_bc12_split(const double (&c)[6], double v) {
+  const double vs = shl3_b(v);
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+  SRBD_DOT6("");
+  double pa, pb;
+  cross_halves((a0 + a1) + a2, pa, pb);
+  return pa + pb;
+}
+// init - the same sum (dot_bc12_sub); init enters half A's accumulator only (upper: this lane is in half B)
+__device__ __forceinline__ double dot_bc12_sub_split(const double (&c)[6], double v, double init, bool upper) {
+  const double vs = shl3_b(v);
+  double a0 = upper ? 0.0 : init, a1 = 0.0, a2 = 0.0;
+  SRBD_DOT6("-");
+  double pa, pb;
+  cross_halves((a0 + a1) + a2, pa, pb);
+  return pa + pb;
+}
+
 }  // namespace srbd

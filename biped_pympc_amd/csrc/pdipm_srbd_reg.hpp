@@ -32,10 +32,6 @@
 // N = 10) and each failing several times more parity-campaign cases (round 6)
 #define SRBD_REFINE_COMBINED 0
 #endif
-#ifndef SRBD_SWP_INV
-#define SRBD_SWP_INV 0  // two-wave QPs invert their chain blocks by the software-pipelined sweep: measured slower, off
-#endif
-
 namespace srbd {
 
 // Threads per QP: one wave at N <= 10 (LDS and registers allow 2 QPs per SIMD); two waves beyond
@@ -135,7 +131,9 @@ __host__ __device__ constexpr int dv_pos(int i) {
 // One symmetric 12x12 stage block: 78 distinct elements in 80 double slots. The slot of element
 // (r, c) = (c, r) is kDvSlot[packed index r(r+1)/2 + c] (scripts/dv_slots.py): in every column the
 // 12 rows sit in distinct slots mod 16, and the two twisted groups' blocks of a step are 80 doubles
-// (= 16 mod 32) apart, so the 24 lanes of a chain load or store hit 24 distinct LDS bank pairs
+// (= 16 mod 32) apart, so the 24 lanes that read or write one column in a chain load or store (one
+// half of the wave: a ds_read_b64 serves 32 lanes per pass, and each half accesses one column of its
+// two groups' blocks) hit 24 distinct LDS bank pairs
 // (the packed layout with stride 78 averaged 2.4 bank cycles per access). Every access to a block
 // goes through this map: the per-lane offset tables below and the S_ii build's entry slots.
 constexpr int kDvStride = 80;
@@ -151,37 +149,7 @@ static __constant__ uint8_t c_dvslot[78] = {77, 58, 32, 73, 46, 5,  52, 54, 50, 
                                             63, 7,  11, 12, 72, 10, 35, 25, 4,  16, 34, 62, 38, 13};
 
 
-// Byte offset, inside a step's block pair, of element (row r, column c) of chain lane l (group
-// g = l >> 4, row r = min(l & 15, 11), both in the group's coordinates): packed-lower slot of
-// (pi^g r, pi^g c) + 624 g. One row of 12 per lane, read once per phase instead of recomputed.
-struct ChainOffs {
-  uint32_t o[32][12];
-};
 constexpr int sym_idx_c(int a, int b) { return a >= b ? a * (a + 1) / 2 + b : b * (b + 1) / 2 + a; }
-constexpr ChainOffs make_chain_offs() {
-  ChainOffs t{};
-  for (int l = 0; l < 32; ++l) {
-    const int g = l >> 4, r = (l & 15) < 12 ? (l & 15) : 11;
-    const int pr = g ? perm12c(r) : r;
-    for (int c = 0; c < 12; ++c)
-      t.o[l][c] = (uint32_t)(8 * kDvSlot[sym_idx_c(pr, g ? perm12c(c) : c)] + kDvBytes * g);
-  }
-  return t;
-}
-static __constant__ ChainOffs c_choffs = make_chain_offs();
-
-// this chain lane's 12 offsets (three 16-byte loads from the constant table)
-__device__ __forceinline__ void load_chain_offs(int lane, uint32_t (&offs)[12]) {
-  const uint4* p = reinterpret_cast<const uint4*>(c_choffs.o[lane & 31]);
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const uint4 v = p[q];
-    offs[4 * q] = v.x;
-    offs[4 * q + 1] = v.y;
-    offs[4 * q + 2] = v.z;
-    offs[4 * q + 3] = v.w;
-  }
-}
 // double at DV byte offset off + imm (imm compile-time: folded into the ds instruction)
 __device__ __forceinline__ double& dv_at(double* DV, uint32_t off, int imm) {
   return *reinterpret_cast<double*>(reinterpret_cast<char*>(DV) + off + imm);
@@ -252,6 +220,102 @@ __device__ __forceinline__ void v_rows(double (&V)[12], const double (&Dr)[12], 
       : "=&v"(V[6]), "=&v"(V[7]), "=&v"(V[8]), "=&v"(V[9]), "=&v"(V[10]), "=&v"(V[11])
       : "0"(0.0), "1"(0.0), "2"(0.0), "3"(0.0), "4"(0.0), "5"(0.0), "v"(d), "v"(Dr[6]), "v"(Dr[7]), "v"(Dr[8]),
         "v"(Dr[9]), "v"(Dr[10]), "v"(Dr[11]));
+}
+
+// ---- the split forms (dpp_rows.hpp: a block's columns {0,1,2,6,7,8} in half A of the wave,
+// {3,4,5,9,10,11} in half B, slot j = column split_col(h, j)) ----
+// C's block structure keeps each half to itself: columns 0..2 of V = D^-1 C^T need Dr's columns 0..2 and
+// 6..8 (all in A), columns 3..5 need 3..5 and 9..11 (all in B), columns 6..11 only themselves.
+// The coefficients of V's column are broadcast from one lane for both halves, so half B keeps row
+// c + 3's coefficients in lane c (SplitCoef: lanes 0,1,2,6,7,8 of both halves hold the coupling row of
+// their slot's column). With x = (a0, a1, a2) in half A and x_k = b [k == c] in half B (lane c < 3),
+//   V[j] = Dl[j] d + Dl[3] x0 + Dl[4] x1 + Dl[5] x2  (j < 3, from lane j),   V[j] = Dl[j] d  (j >= 3, from lane j + 3)
+// is v_rows' FMA sequence per element in both halves (half B's two extra terms add an exact zero to a
+// sum that started from +0: the same bits for finite Dl).
+struct SplitCoef {
+  double d, x0, x1, x2;
+};
+__device__ __forceinline__ void v_rows_split(double (&V)[6], const double (&Dl)[6], const SplitCoef& k) {
+  asm("s_nop 1\n"
+      SRBD_FMAC_BC("%0", "%6", "%10", 0) SRBD_FMAC_BC("%1", "%6", "%11", 1) SRBD_FMAC_BC("%2", "%6", "%12", 2)
+      SRBD_FMAC_BC("%0", "%7", "%13", 0) SRBD_FMAC_BC("%1", "%7", "%13", 1) SRBD_FMAC_BC("%2", "%7", "%13", 2)
+      SRBD_FMAC_BC("%0", "%8", "%14", 0) SRBD_FMAC_BC("%1", "%8", "%14", 1) SRBD_FMAC_BC("%2", "%8", "%14", 2)
+      SRBD_FMAC_BC("%0", "%9", "%15", 0) SRBD_FMAC_BC("%1", "%9", "%15", 1) SRBD_FMAC_BC("%2", "%9", "%15", 2)
+      SRBD_ASM_TAIL
+      : "=&v"(V[0]), "=&v"(V[1]), "=&v"(V[2])
+      : "0"(0.0), "1"(0.0), "2"(0.0), "v"(k.d), "v"(k.x0), "v"(k.x1), "v"(k.x2), "v"(Dl[0]), "v"(Dl[1]), "v"(Dl[2]),
+        "v"(Dl[3]), "v"(Dl[4]), "v"(Dl[5]));
+  asm("s_nop 1\n"
+      SRBD_FMAC_BC("%0", "%6", "%7", 6) SRBD_FMAC_BC("%1", "%6", "%8", 7) SRBD_FMAC_BC("%2", "%6", "%9", 8)
+      SRBD_ASM_TAIL
+      : "=&v"(V[3]), "=&v"(V[4]), "=&v"(V[5])
+      : "0"(0.0), "1"(0.0), "2"(0.0), "v"(k.d), "v"(Dl[3]), "v"(Dl[4]), "v"(Dl[5]));
+}
+// fmac_rows678_4 for the six slots of a half: acc[i] (+/-)= v[i](lane 6) c6 + v[i](lane 7) c7 + v[i](lane 8) c8
+#define SRBD_ROWS678_6(N6, N7, N8)                                                                    \
+  asm("s_nop 1\n"                                                                                     \
+      SRBD_FMAC_BC("%0", "%6", N6, 6) SRBD_FMAC_BC("%1", "%7", N6, 6) SRBD_FMAC_BC("%2", "%8", N6, 6)   \
+      SRBD_FMAC_BC("%3", "%9", N6, 6) SRBD_FMAC_BC("%4", "%10", N6, 6) SRBD_FMAC_BC("%5", "%11", N6, 6) \
+      SRBD_FMAC_BC("%0", "%6", N7, 7) SRBD_FMAC_BC("%1", "%7", N7, 7) SRBD_FMAC_BC("%2", "%8", N7, 7)   \
+      SRBD_FMAC_BC("%3", "%9", N7, 7) SRBD_FMAC_BC("%4", "%10", N7, 7) SRBD_FMAC_BC("%5", "%11", N7, 7) \
+      SRBD_FMAC_BC("%0", "%6", N8, 8) SRBD_FMAC_BC("%1", "%7", N8, 8) SRBD_FMAC_BC("%2", "%8", N8, 8)   \
+      SRBD_FMAC_BC("%3", "%9", N8, 8) SRBD_FMAC_BC("%4", "%10", N8, 8) SRBD_FMAC_BC("%5", "%11", N8, 8) \
+      SRBD_ASM_TAIL                                                                                     \
+      : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5])                        \
+      : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(c6), "v"(c7), "v"(c8))
+template <bool kNeg = false>
+__device__ __forceinline__ void fmac_rows678_6(double (&x)[6], const double (&v)[6], double c6, double c7, double c8) {
+  if constexpr (kNeg)
+    SRBD_ROWS678_6("-%12", "-%13", "-%14");
+  else
+    SRBD_ROWS678_6("%12", "%13", "%14");
+}
+
+// Byte offsets, inside a step's block pair, of chain lane l (half h = l >> 5, group g = (l >> 4) & 1,
+// row r = min(l & 15, 11), both in the group's coordinates) for its six slots: for loads, element (row r,
+// column split_col(h, j)) = packed-lower slot of (pi^g r, pi^g c) + 624 g -- one row per lane, read once
+// per phase instead of recomputed; for stores the same except where the packed symmetric store must lose.
+// Slot {r, c} keeps the element computed by row min(r, c), as the 12-column store order (later wins)
+// leaves it: store instruction j writes columns split_col(0, j) and split_col(1, j), so the row-max(r, c)
+// copy loses by order when its column's instruction comes first and is otherwise sent to one of the
+// block's two unused slots (kDvSink: never read) -- no slot that is read depends on the order in which
+// the hardware takes the lanes of one store instruction.
+constexpr int kDvSink[2] = {17, 47};
+struct ChainOffsSplit {
+  uint32_t o[64][12];  // [0..5] loads, [6..11] stores
+};
+constexpr bool dv_slot_used(int s) {
+  for (int k = 0; k < 78; ++k)
+    if (kDvSlot[k] == s) return true;
+  return false;
+}
+static_assert(!dv_slot_used(kDvSink[0]) && !dv_slot_used(kDvSink[1]), "the sinks are unused block slots");
+constexpr ChainOffsSplit make_chain_offs_split() {
+  ChainOffsSplit t{};
+  for (int l = 0; l < 64; ++l) {
+    const int h = l >> 5, g = (l >> 4) & 1, r = (l & 15) < 12 ? (l & 15) : 11;
+    const int pr = g ? perm12c(r) : r;
+    const int jr = r % 3 + (r >= 6 ? 3 : 0);  // the store instruction that writes column r (in r's half)
+    for (int j = 0; j < 6; ++j) {
+      const int c = split_col(h, j);
+      const bool lose = r > c && j >= jr;  // the winner (row c, column r) is stored no later: sink
+      t.o[l][j] = (uint32_t)(8 * kDvSlot[sym_idx_c(pr, g ? perm12c(c) : c)] + kDvBytes * g);
+      t.o[l][6 + j] = lose ? (uint32_t)(8 * kDvSink[r & 1] + kDvBytes * g) : t.o[l][j];
+    }
+  }
+  return t;
+}
+static __constant__ ChainOffsSplit c_choffs_split = make_chain_offs_split();
+// this split chain lane's six load offsets and (kStore) six store offsets
+template <bool kStore>
+__device__ __forceinline__ void load_chain_offs_split(int lane, uint32_t (&ld)[6], uint32_t (&st)[6]) {
+  const uint4* p = reinterpret_cast<const uint4*>(c_choffs_split.o[lane & 63]);
+  const uint4 a = p[0], b = p[1];
+  ld[0] = a.x, ld[1] = a.y, ld[2] = a.z, ld[3] = a.w, ld[4] = b.x, ld[5] = b.y;
+  if constexpr (kStore) {
+    const uint4 c = p[2];
+    st[0] = b.z, st[1] = b.w, st[2] = c.x, st[3] = c.y, st[4] = c.z, st[5] = c.w;
+  }
 }
 
 // (C w)_r and (C^T y)_r of the compact stage coupling for one vector held one element per lane:
@@ -426,10 +490,6 @@ struct RegCtx {
     }
   }
   static constexpr int mid = N / 2, nf = mid, nb = N - 1 - mid, T = nf > nb ? nf : nb;
-  // the chain's 12x12 block inverses by the software-pipelined sweep (inverse_rows12<true>), tried for
-  // two-wave QPs on the premise that their chain wave runs alone on its SIMD (profiles/r05/simd_probe.txt:
-  // its SIMD partner is another QP's second wave); measured +2.1 % at N = 20 (n20_pipeline.txt): off
-  static constexpr bool kSwpInv = SRBD_SWP_INV && TPB == 128;
   static constexpr int kFactorUnroll = T + 1;  // chains fully unrolled (N = 20: -4.7 % vs rolled)
   double* L;
   int lane;
@@ -798,99 +858,92 @@ struct RegCtx {
 
   // kFwd: also the affine solve's forward elimination w_i = D_i^-1 (g_i - C w_{i-1}) with each
   // block's inverse row still in registers (g from solve_rhs(0) in QV; w_i written back over g_i)
+  // Twisted block recursion (see pdipm_srbd.hpp FastCtx::factor) on the 64 lanes of wave 0: group 0
+  // (DPP rows 0 and 2) forward, group 1 (DPP rows 1 and 3) backward in pi-permuted coordinates, middle
+  // block by group 0. Lanes l and l + 32 hold one row of a group's block, six columns each (dpp_rows.hpp
+  // split_col): row r of V = D^-1 Cg^T is computed by the two lanes of row r; X = Cg V needs rows
+  // {r, 6, 7, 8} (r < 3) or {r, r + 6} (3 <= r < 6) of the lane's own columns, fetched with row_newbcast /
+  // row_shl:6 DPP; group 1's middle term reaches group 0 through ds_bpermute. The coupling vectors (g, w)
+  // stay one element per row, held with the same bits in both halves (fwd_rhs).
   template <bool kFwd>
   SRBD_PHASE_ATTR __device__ void factor_chain() {
     const int lane = fresh_lane();
     double* DV = at(Lo::DV);
     double* QV = at(Lo::QV);
-    // Twisted block recursion (see pdipm_srbd.hpp FastCtx::factor): group 0 (lanes 0..15) forward,
-    // group 1 (lanes 16..31) backward in pi-permuted coordinates, middle block by group 0. Row r of
-    // V = D^-1 Cg^T is computed by lane r; X = Cg V needs rows {r, 6, 7, 8} (r < 3) or {r, r + 6}
-    // (3 <= r < 6), fetched with row_newbcast / row_shl:6 DPP; group 1's middle term reaches
-    // group 0 through ds_bpermute.
-    if (lane < 32) {
-      const int g = lane >> 4, l16 = lane & 15;
+    if (lane < 64) {
+      const int h = lane >> 5, g = (lane >> 4) & 1, l16 = lane & 15;
       const int r = l16 < 12 ? l16 : 11;
       const int pr = g ? perm12(r) : r;
       const int cnt = g ? nb : nf;
       const double* cc = at(Lo::Cc) + 24 * g;
-      // the coupling row's coefficients loaded from clamped indices and selected (a conditional
-      // load is an exec-mask round trip per coefficient)
       const double crd = cc[r];
       const bool ra = r < 3, rb = r >= 3 && r < 6;
       const int r3 = ra ? r : 0, r6 = rb ? r : 3;
       const double la0 = cc[12 + 3 * r3], la1 = cc[13 + 3 * r3], la2 = cc[14 + 3 * r3], lb = cc[21 + r6 - 3];
       const double cra0 = ra ? la0 : 0.0, cra1 = ra ? la1 : 0.0, cra2 = ra ? la2 : 0.0;
       const double crb = rb ? lb : 0.0;
-      uint32_t offs[12];  // byte offset of (pr, column c in group coordinates) in a step's blocks
-      load_chain_offs(lane, offs);
+      // v_rows_split's broadcast coefficients: half B's lanes 0,1,2,6,7,8 hold rows 3,4,5,9,10,11
+      const bool up = h != 0, b3 = (r % 6) < 3;
+      const double kb = cc[21 + r3];  // (r + 3, r + 9) for r < 3
+      const SplitCoef kc{cc[r + ((up && b3) ? 3 : 0)], up ? ((ra && r == 0) ? kb : 0.0) : cra0,
+                         up ? ((ra && r == 1) ? kb : 0.0) : cra1, up ? ((ra && r == 2) ? kb : 0.0) : cra2};
+      uint32_t offs[6], sto[6];
+      load_chain_offs_split<true>(lane, offs, sto);
       const CoupleRow Cr{crd, crb, cra0, cra1, cra2};
-      double wf = 0.0;  // forward-elimination vector of the fused affine solve
-      double Dr[12];
+      double wf = 0.0;
+      double Dr[6];
 #pragma unroll
-      for (int c = 0; c < 12; ++c) Dr[c] = 0.0;
+      for (int c = 0; c < 6; ++c) Dr[c] = 0.0;
 #pragma unroll kFactorUnroll
       for (int t = 0; t <= T; ++t) {
         const bool mstep = (t == T);
         const int i = mstep ? mid : (g ? N - 1 - t : t);
         const bool act = mstep ? true : (t < cnt);
         const bool prev = mstep ? (cnt >= 1) : (t >= 1);
-        double Sr[12], X[12];
+        double Sr[6], X[6];
 #pragma unroll
-        for (int c = 0; c < 12; ++c) X[c] = 0.0;
-        const int imm = mstep ? kDvBytes * (N - 1) : 2 * kDvBytes * t;  // this step's blocks
+        for (int c = 0; c < 6; ++c) X[c] = 0.0;
+        const int imm = mstep ? kDvBytes * (N - 1) : 2 * kDvBytes * t;
         if (act) {
           if (!(mstep && g == 1)) {
 #pragma unroll
-            for (int c = 0; c < 12; ++c) Sr[c] = dv_at(DV, offs[c], imm);
+            for (int c = 0; c < 6; ++c) Sr[c] = dv_at(DV, offs[c], imm);
           }
           if (prev) {
-            double V[12];
-            // V[c] = sum_k Dr[k] C[c][k]: row c of C is lane c's own coupling row (crd, cra*, crb),
-            // broadcast inside the FMAs (row_newbcast:c) instead of re-read from LDS every step
-            v_rows(V, Dr, crd, cra0, cra1, cra2, crb);
-            if (!mstep) {  // S - X accumulated in place
+            double V[6];
+            v_rows_split(V, Dr, kc);
+            if (!mstep) {
 #pragma unroll
-              for (int c = 0; c < 12; ++c) Sr[c] = (Sr[c] - crd * V[c]) - crb * shl6(V[c]);
+              for (int c = 0; c < 6; ++c) Sr[c] = (Sr[c] - crd * V[c]) - crb * shl6(V[c]);
+              fmac_rows678_6<true>(Sr, V, cra0, cra1, cra2);
+            } else {
 #pragma unroll
-              for (int c = 0; c < 12; c += 4)  // - rows 6..8 of V through fused broadcast-FMAs
-                fmac_rows678_4<true>(Sr[c], Sr[c + 1], Sr[c + 2], Sr[c + 3], V[c], V[c + 1], V[c + 2], V[c + 3],
-                                     cra0, cra1, cra2);
-            } else {  // middle step: group 1's X is handed to group 0 below
-#pragma unroll
-              for (int c = 0; c < 12; ++c) X[c] = crd * V[c] + crb * shl6(V[c]);
-#pragma unroll
-              for (int c = 0; c < 12; c += 4)  // + rows 6..8 of V through fused broadcast-FMAs
-                fmac_rows678_4(X[c], X[c + 1], X[c + 2], X[c + 3], V[c], V[c + 1], V[c + 2], V[c + 3], cra0,
-                               cra1, cra2);
+              for (int c = 0; c < 6; ++c) X[c] = crd * V[c] + crb * shl6(V[c]);
+              fmac_rows678_6(X, V, cra0, cra1, cra2);
               if (g == 0) {
 #pragma unroll
-                for (int c = 0; c < 12; ++c) Sr[c] -= X[c];
+                for (int c = 0; c < 6; ++c) Sr[c] -= X[c];
               }
             }
           }
         }
-        if (mstep && nb >= 1) {  // X_b[r][c] = X'[pi r][pi c], held by lane 16 + pi(r)
+        if (mstep && nb >= 1) {  // X_b[r][c] = X'[pi r][pi c]: the same half's lane 16 + pi(r), slot j +- 3
 #pragma unroll
-          for (int c = 0; c < 12; ++c) {
-            const double xb = __shfl(X[perm12c(c)], 16 + perm12(r), 64);
+          for (int c = 0; c < 6; ++c) {
+            const double xb = __shfl(X[(c + 3) % 6], (lane & 32) + 16 + perm12(r), 64);
             if (g == 0) Sr[c] -= xb;
           }
         }
         if (act && !(mstep && g == 1)) {
-          inverse_rows12<kSwpInv>(Sr, Dr);
-          // every lane writes its whole row: (r, c) and (c, r) share a packed slot, so each slot is
-          // written twice with the two (rounding-different) halves of the symmetric inverse; the
-          // later ds_write in program order wins, deterministically (shadow lanes 12..15 repeat row
-          // 11 bit for bit). Cheaper than 12 per-element exec-masked stores.
+          inverse_rows12_split(Sr, Dr);
 #pragma unroll
-          for (int c = 0; c < 12; ++c) dv_at(DV, offs[c], imm) = Dr[c];
+          for (int c = 0; c < 6; ++c) dv_at(DV, sto[c], imm) = Dr[c];  // the packed store: ChainOffsSplit
         }
-        if constexpr (kFwd) {  // the solve chain's forward step t (solve_chain), Dr = D_i^-1 row
+        if constexpr (kFwd) {
           const double q = fwd_rhs(act, prev, mstep, g, r, Cr, wf, QV + 12 * i + pr);
           if (act && !(mstep && g == 1)) {
-            wf = dot_bc12(Dr, q);
-            QV[12 * i + pr] = wf;  // shadow lanes 12..15 store row 11's value bit for bit
+            wf = dot_bc12_split(Dr, q);
+            QV[12 * i + pr] = wf;  // both halves and the shadow lanes store the same bits
           }
         }
       }
@@ -1103,23 +1156,25 @@ struct RegCtx {
   }
 
   // Twisted block solve (pdipm_srbd.hpp FastCtx::solve), w / v in registers. kBackOnly: the
-  // forward elimination already ran in factor_chain<true>, which left w of every step in QV.
+  // forward elimination already ran in factor_chain<true>, which left w of every step in QV. On the 64
+  // lanes of wave 0, a block's row split over lanes l and l + 32 as in factor_chain.
   template <bool kBackOnly>
   SRBD_PHASE_ATTR __device__ void solve_chain() {
     const int lane = fresh_lane();
     double* QV = at(Lo::QV);
     const double* DV = at(Lo::DV);
-    if (lane < 32) {
-      const int g = lane >> 4, l16 = lane & 15;
+    if (lane < 64) {
+      const int g = (lane >> 4) & 1, l16 = lane & 15;
+      const bool up = (lane >> 5) != 0;
       const int r = l16 < 12 ? l16 : 11;
       const bool own = l16 < 12;
       const int pr = g ? perm12(r) : r;
       const int cnt = g ? nb : nf;
       const double* cc = at(Lo::Cc) + 24 * g;
-      CoupleRow Cr, Ct;  // row r of Cg and of Cg^T (compact layout, see the header)
-      uint32_t offs[12];
-      load_chain_offs(lane, offs);
-      {  // coefficients loaded from clamped indices and selected (no conditional loads)
+      CoupleRow Cr, Ct;
+      uint32_t offs[6], unused[6];
+      load_chain_offs_split<false>(lane, offs, unused);
+      {
         const bool ra = r < 3, rb = r >= 3 && r < 6, ta = r >= 6 && r < 9, tb = r >= 9;
         const int r3 = ra ? r : 0, r6 = rb ? r : 3, t6 = ta ? r : 6, t9 = tb ? r : 9;
         const double la0 = cc[12 + 3 * r3], la1 = cc[13 + 3 * r3], la2 = cc[14 + 3 * r3], lb = cc[21 + r6 - 3];
@@ -1135,10 +1190,10 @@ struct RegCtx {
         Ct.a1 = ta ? ka1 : 0.0;
         Ct.a2 = ta ? ka2 : 0.0;
       }
-      double w = 0.0, wv[T + 1];  // w / v per elimination step, indexed through selects
+      double w = 0.0, wv[T + 1];
 #pragma unroll
       for (int k = 0; k <= T; ++k) wv[k] = 0.0;
-      if constexpr (kBackOnly) {  // w of every step from QV (stage i, element pr), mid included
+      if constexpr (kBackOnly) {
 #pragma unroll
         for (int t = 0; t < T; ++t)
           if (t < cnt) wv[t] = QV[12 * (g ? N - 1 - t : t) + pr];
@@ -1153,31 +1208,28 @@ struct RegCtx {
         const double q = fwd_rhs(act, prev, mstep, g, r, Cr, w, QV + 12 * i + pr);
         if (act && !(mstep && g == 1)) {
           const int imm = mstep ? kDvBytes * (N - 1) : 2 * kDvBytes * t;
-          double Dr[12];
+          double Dr[6];
 #pragma unroll
-          for (int k = 0; k < 12; ++k) Dr[k] = dv_at(DV, offs[k], imm);
-          w = dot_bc12(Dr, q);
+          for (int k = 0; k < 6; ++k) Dr[k] = dv_at(DV, offs[k], imm);
+          w = dot_bc12_split(Dr, q);
 #pragma unroll
           for (int k = 0; k <= T; ++k) wv[k] = (k == t) ? w : wv[k];
         }
       }
-      // outward substitution from y_mid (group 0's last w; group 1 fetches row pi(r) of it)
       double y = w;
       if constexpr (!kBackOnly) {
         const double ym = __shfl(w, perm12(r), 64);
         if (own && g == 0) QV[12 * mid + r] = w;
         y = g ? ym : w;
       }
-      // step te walks back from each group's last elimination step: both groups' blocks of step te
-      // sit at 1248 te, and w_te is register wv[te]
 #pragma unroll
       for (int te = T - 1; te >= 0; --te) {
         if (te < cnt) {
           const int i = g ? N - 1 - te : te;
-          double Dr[12];
+          double Dr[6];
 #pragma unroll
-          for (int k = 0; k < 12; ++k) Dr[k] = dv_at(DV, offs[k], 2 * kDvBytes * te);
-          y = dot_bc12_sub(Dr, couple_cty2(Ct, y), wv[te]);  // w_te - D^-1 Cg^T y_prev
+          for (int k = 0; k < 6; ++k) Dr[k] = dv_at(DV, offs[k], 2 * kDvBytes * te);
+          y = dot_bc12_sub_split(Dr, couple_cty2(Ct, y), wv[te], up);
           if (own) QV[12 * i + pr] = y;
         }
       }
