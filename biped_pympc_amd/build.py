@@ -132,7 +132,7 @@ def build_dropin(kind: str, N: int, K: int | None) -> str:
 # the HIP translation units of libsrbd_mpc.so and their unit-specific flags: the N = 20 register
 # kernels in their own unit, scheduled with the register-pressure trackers (csrc/reg20.hpp)
 HIP_UNITS = {
-    "srbd_mpc.hip": ["-DSRBD_SPLIT_REG20"],
+    "srbd_mpc.hip": [],
     "srbd_reg20.hip": ["-mllvm", "-amdgpu-use-amdgpu-trackers=1"],
     "srbd_regN.hip": ["-mllvm", "-amdgpu-use-amdgpu-trackers=1"],  # the other register horizons
     "srbd_backward.hip": [],  # the backward pass: adjoint KKT solve, QP-data gradients, former / prep / wrench VJPs

@@ -492,12 +492,11 @@ __global__ __launch_bounds__(64) void pdipm_backward_multi_kernel(BackwardMultiA
 }
 
 namespace bwd {
-// host side of the backward translation unit (srbd_backward.hip)
+// host side of the backward translation unit (srbd_backward.hip): the kernels as the main unit launches
+// them, 64 threads per env with backward_lds_bytes(N) of dynamic LDS
 // full: the instantiation that takes every cotangent; otherwise grad_x alone
-const void* adjoint_kernel(bool full);
-void launch_adjoint(const BackwardArgs& a, bool full, size_t lds, hipStream_t s);
-const void* adjoint_multi_kernel(bool full);
-void launch_adjoint_multi(const BackwardMultiArgs& a, bool full, size_t lds, hipStream_t s);
+const void* adjoint_kernel(bool full);        // (BackwardArgs)
+const void* adjoint_multi_kernel(bool full);  // (BackwardMultiArgs)
 }  // namespace bwd
 
 }  // namespace srbd

@@ -10,11 +10,9 @@
 namespace srbd {
 struct FusedArgs;
 namespace regn {
-bool supported(int N);        // a register kernel instantiated here for this horizon
-size_t lds_bytes(int N);      // RegLayout<N> in bytes
-const void* solver_kernel(int N);
-const void* step_kernel(int N);
-// static LDS (RegLayout<N>): launched with 0 dynamic bytes
+bool supported(int N);  // a register kernel instantiated here for this horizon
+// static LDS (RegLayout<N>): launched with 0 dynamic bytes. For a supported horizon only: any other
+// launches nothing.
 void launch_solver(int N, const SolverArgs& a, hipStream_t s);
 void launch_step(int N, const FusedArgs& a, hipStream_t s);
 }  // namespace regn

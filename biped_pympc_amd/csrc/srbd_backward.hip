@@ -17,18 +17,8 @@ const void* adjoint_kernel(bool full) {
   return full ? (const void*)pdipm_backward_kernel<0, true> : (const void*)pdipm_backward_kernel<0, false>;
 }
 
-void launch_adjoint(const BackwardArgs& a, bool full, size_t lds, hipStream_t s) {
-  if (full) hipLaunchKernelGGL((pdipm_backward_kernel<0, true>), dim3(a.batch), dim3(64), lds, s, a);
-  else hipLaunchKernelGGL((pdipm_backward_kernel<0, false>), dim3(a.batch), dim3(64), lds, s, a);
-}
-
 const void* adjoint_multi_kernel(bool full) {
   return full ? (const void*)pdipm_backward_multi_kernel<0, true> : (const void*)pdipm_backward_multi_kernel<0, false>;
-}
-
-void launch_adjoint_multi(const BackwardMultiArgs& a, bool full, size_t lds, hipStream_t s) {
-  if (full) hipLaunchKernelGGL((pdipm_backward_multi_kernel<0, true>), dim3(a.batch), dim3(64), lds, s, a);
-  else hipLaunchKernelGGL((pdipm_backward_multi_kernel<0, false>), dim3(a.batch), dim3(64), lds, s, a);
 }
 
 void launch_former_backward(const FormerBackwardArgs& a, hipStream_t s) {

@@ -1,7 +1,7 @@
 // srbd_mpc.hip -- libsrbd_mpc.so: HIP kernels (gfx950) + the C-ABI of include/srbd_mpc.h.
 //
-// The main translation unit; the N = 20 register kernels are built apart in srbd_reg20.hip when
-// SRBD_SPLIT_REG20 is defined (the product build, biped_pympc_amd/build.py). The constant-memory
+// The main translation unit; the register kernels at the horizons other than 10 are built apart in
+// srbd_reg20.hip and srbd_regN.hip, the backward kernels in srbd_backward.hip. The constant-memory
 // tables (srbd_common.hpp) are compile-time initialised, so each unit's copy is identical.
 #include <hip/hip_runtime.h>
 
@@ -55,7 +55,64 @@ constexpr int kErrInvalid = (int)hipErrorInvalidValue;
 // can hold resident of any stage-invariant kernel (at most 8 QPs per CU: the N <= 10 register kernels)
 constexpr int kMaxQpsPerCu = 8;
 
+// an argument the entry `what` rejects: "<what>: <msg>"
+int fail(const char* what, const char* msg) { return set_error(kErrInvalid, (std::string(what) + ": " + msg).c_str()); }
+
+// no HIP device is current, or its index is past the per-device state: as the setter `what` reports it,
+// or (null) as a launch does on behalf of any entry
+int no_device(const char* what = nullptr) {
+  const std::string msg = what ? std::string(what) + ": no current HIP device" : "no current HIP device (or index >= 64)";
+  return set_error((int)hipErrorInvalidDevice, msg.c_str());
+}
+
+// the result of the launch just enqueued; `what` names its kernel ("<kernel> launch")
+int launched(const char* what) {
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : set_error((int)e, what);
+}
+
+// the n device pointers of a caller's table into kernel arguments; a null one is the entry's "<what>: <msg>"
+template <class Dst, class Src>
+int copy_pointers(const char* what, const char* msg, Dst* dst, Src* const* src, int n) {
+  for (int i = 0; i < n; ++i) {
+    if (!src[i]) return fail(what, msg);
+    dst[i] = src[i];
+  }
+  return 0;
+}
+
 bool horizon_ok(int N) { return N >= 1 && N <= srbd::kMaxN; }
+
+// The six arrays of a QP as the former writes them -- H, f, A, b, G, d -- and how a workspace of a batch
+// of them is laid out: array after array, each (rows, width).
+struct QpLayout {
+  size_t width[6];  // doubles per QP
+  explicit QpLayout(int horizon) {
+    const size_t N = (size_t)horizon;
+    const size_t w[6] = {24 * N, 24 * N, 122 * N - 24, 14 * N, 28 * N, 16 * N};
+    std::copy(w, w + 6, width);
+  }
+  // doubles of `rows` rows of every array in `mask` (bit i = array i)
+  size_t doubles(size_t rows = 1, unsigned mask = 63u) const {
+    size_t n = 0;
+    for (int i = 0; i < 6; ++i)
+      if (mask >> i & 1u) n += rows * width[i];
+    return n;
+  }
+  // slot[i] = the next `rows` rows of array i at `p`, which moves past them; null for an array not in `mask`
+  void carve(double*& p, size_t rows, double* (&slot)[6], unsigned mask = 63u) const {
+    for (int i = 0; i < 6; ++i) {
+      slot[i] = (mask >> i & 1u) ? p : nullptr;
+      if (slot[i]) p += rows * width[i];
+    }
+  }
+};
+
+// the former's six arrays in the solver's input order H, G, A, f, d, b: its input slots 0..5
+void solver_order(double* const (&qp)[6], const double* (&in)[10]) {
+  constexpr int kFormerSlot[6] = {0, 4, 2, 1, 5, 3};
+  for (int i = 0; i < 6; ++i) in[i] = qp[kFormerSlot[i]];
+}
 
 size_t solver_lds_bytes(int N) { return sizeof(double) * (size_t)srbd::SolverLayout(N).total; }
 size_t fast_lds_bytes(int N) { return sizeof(double) * (size_t)srbd::FastLayout(N).total; }
@@ -121,22 +178,44 @@ void set_info_args(Args& a, const srbd_solve_info* info) {
 }
 srbd_solve_info status_only(int* status) { return srbd_solve_info{status, nullptr, nullptr}; }
 
-int ensure_lds_attr(const void* fn, size_t bytes, srbd::LdsAttr& cache) {
+// A kernel taking Args that keeps its problem in dynamic LDS, and the largest size configured for it per
+// device. A kernel of this unit gives Args itself; one of another unit comes as the handle its unit
+// exports, with Args named where the LdsKernel is declared.
+template <class Args>
+struct LdsKernel {
+  const void* fn;
+  const char* what;       // "<kernel> launch"
+  const char* too_large;  // the message for a horizon whose problem does not fit a workgroup's LDS
+  srbd::LdsAttr cfg{};
+  LdsKernel(void (*kernel)(Args), const char* what, const char* too_large)
+      : fn((const void*)kernel), what(what), too_large(too_large) {}
+  LdsKernel(const void* handle, const char* what, const char* too_large)
+      : fn(handle), what(what), too_large(too_large) {}
+};
+
+// Launch of such a kernel, one workgroup of `threads` per problem of a.batch, with `lds` bytes: the
+// 160 KiB a workgroup can have, the kernel's attribute on the current device (set when `lds` exceeds
+// what was configured there), the launch and its result.
+template <class Args>
+int launch_dynamic_lds(LdsKernel<Args>& k, int threads, size_t lds, const Args& a, hipStream_t s) {
+  if (lds > 160 * 1024) return set_error(kErrInvalid, k.too_large);
   const int dev = current_device();
-  if (dev < 0) return set_error((int)hipErrorInvalidDevice, "no current HIP device (or index >= 64)");
-  if (!cache.claim(dev, bytes)) return 0;
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e != hipSuccess) return set_error((int)e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-  cache.commit(dev, bytes);
-  return 0;
+  if (dev < 0) return no_device();
+  if (k.cfg.claim(dev, lds)) {
+    hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return set_error((int)e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
+    k.cfg.commit(dev, lds);
+  }
+  void* argv[] = {const_cast<Args*>(&a)};
+  (void)hipLaunchKernel(k.fn, dim3(a.batch), dim3(threads), argv, lds, s);
+  return launched(k.what);
 }
 
 int launch_former(const srbd::FormerArgs& a, hipStream_t s) {
   if (a.batch == 0) return 0;
   const int grid = (a.batch + kFormerWaves - 1) / kFormerWaves;
   hipLaunchKernelGGL(srbd::qp_former_kernel<kFormerWaves>, dim3(grid), dim3(64 * kFormerWaves), 0, s, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : set_error((int)e, "qp_former_kernel launch");
+  return launched("qp_former_kernel launch");
 }
 
 // The per-device scratch pool of the stage-invariant solver kernels (pdipm.hpp
@@ -203,7 +282,7 @@ ScratchPool* scratch_pool(hipStream_t s, bool check_capture, int& rc) {
   std::lock_guard<std::mutex> lock(g_scratch_mu);
   ScratchPool* pool = g_scratch.at(dev);
   if (!pool) {
-    rc = set_error((int)hipErrorInvalidDevice, "no current HIP device (or index >= 64)");
+    rc = no_device();
     return nullptr;
   }
   if (!pool->buf) {
@@ -249,55 +328,41 @@ int attach_scratch(srbd::SolverArgs& a, hipStream_t s) {
   return 0;
 }
 
+// Which stage-invariant kernels serve a horizon -- the one place that knows where each is built. The
+// register kernels: N = 10 in this unit, N = 20 in srbd_reg20.hip, the other horizons they support in
+// srbd_regN.hip; the LDS-resident ones (pdipm_srbd_kernel, mpc_step_lds_kernel) at every other horizon.
+enum class Serves { Reg10, Reg20, RegN, Lds };
+Serves serves(int N) {
+  if (N == 10) return Serves::Reg10;
+  if (N == 20) return Serves::Reg20;
+  return srbd::regn::supported(N) ? Serves::RegN : Serves::Lds;  // RegN: regn::launch_* has this horizon's case
+}
+
 int launch_solver(const srbd::SolverArgs& a0, hipStream_t s) {
   if (a0.batch == 0) return 0;
-  static srbd::LdsAttr cfg_general, cfg_fast, cfg_fast10, cfg_fast20;
+  constexpr const char* kTooLarge = "horizon too large for the LDS-resident solver";
+  static LdsKernel general{srbd::pdipm_kernel, "pdipm_kernel launch", kTooLarge};
   srbd::SolverArgs a = a0;
   set_refinement_args(a);
   const int path = solver_path();
   std::shared_lock<std::shared_mutex> keep_pool(g_pool_rw);  // until the launch is enqueued
+  if (path == 1) return launch_dynamic_lds(general, srbd::kGeneralThreads, solver_lds_bytes(a.N), a, s);
   // the stage-invariant kernels solve any other QP of the batch in the same launch (scratch pool)
-  if (path != 1)
-    if (int rc = attach_scratch(a, s)) return rc;
-  if (path == 0 && srbd::regn::supported(a.N)) {  // the register kernel of another horizon
-    srbd::regn::launch_solver(a.N, a, s);  // static LDS (RegLayout)
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_error((int)e, "pdipm_srbd_reg_kernel launch");
-  }
-  if (path == 0 && (a.N == 10 || a.N == 20)) {
-    if (a.N == 10) {
+  if (int rc = attach_scratch(a, s)) return rc;
+  switch (path == 2 ? Serves::Lds : serves(a.N)) {  // the register kernels' LDS is static (RegLayout)
+    case Serves::Reg10:
       hipLaunchKernelGGL(srbd::pdipm_srbd_reg_kernel<10>, dim3(a.batch), dim3(64), 0, s, a);
-    } else {
-#ifdef SRBD_SPLIT_REG20
-      srbd::reg20::launch_solver(a, s);
-#else
-      hipLaunchKernelGGL(srbd::pdipm_srbd_reg_kernel<20>, dim3(a.batch), dim3(srbd::reg_tpb(20)), 0, s, a);
-#endif
+      break;
+    case Serves::Reg20: srbd::reg20::launch_solver(a, s); break;
+    case Serves::RegN: srbd::regn::launch_solver(a.N, a, s); break;
+    case Serves::Lds: {  // horizon-specialised instantiations for the common horizons, runtime-N otherwise
+      static LdsKernel fast10{srbd::pdipm_srbd_kernel<10>, "pdipm_srbd_kernel launch", kTooLarge};
+      static LdsKernel fast20{srbd::pdipm_srbd_kernel<20>, "pdipm_srbd_kernel launch", kTooLarge};
+      static LdsKernel fast{srbd::pdipm_srbd_kernel<0>, "pdipm_srbd_kernel launch", kTooLarge};
+      return launch_dynamic_lds(a.N == 10 ? fast10 : a.N == 20 ? fast20 : fast, 64, fast_lds_bytes(a.N), a, s);
     }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_error((int)e, "pdipm_srbd_reg_kernel launch");
   }
-  if (path == 0 || path == 2) {
-    const size_t lds = fast_lds_bytes(a.N);
-    if (lds > 160 * 1024) return set_error(kErrInvalid, "horizon too large for the LDS-resident solver");
-    // horizon-specialised instantiations for the common horizons, runtime-N otherwise
-    const void* fn = a.N == 10 ? (const void*)srbd::pdipm_srbd_kernel<10>
-                   : a.N == 20 ? (const void*)srbd::pdipm_srbd_kernel<20>
-                               : (const void*)srbd::pdipm_srbd_kernel<0>;
-    srbd::LdsAttr& cfg = a.N == 10 ? cfg_fast10 : a.N == 20 ? cfg_fast20 : cfg_fast;
-    if (int rc = ensure_lds_attr(fn, lds, cfg)) return rc;
-    if (a.N == 10) hipLaunchKernelGGL(srbd::pdipm_srbd_kernel<10>, dim3(a.batch), dim3(64), lds, s, a);
-    else if (a.N == 20) hipLaunchKernelGGL(srbd::pdipm_srbd_kernel<20>, dim3(a.batch), dim3(64), lds, s, a);
-    else hipLaunchKernelGGL(srbd::pdipm_srbd_kernel<0>, dim3(a.batch), dim3(64), lds, s, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_error((int)e, "pdipm_srbd_kernel launch");
-  }
-  const size_t lds = solver_lds_bytes(a.N);
-  if (lds > 160 * 1024) return set_error(kErrInvalid, "horizon too large for the LDS-resident solver");
-  if (int rc = ensure_lds_attr((const void*)srbd::pdipm_kernel, lds, cfg_general)) return rc;
-  hipLaunchKernelGGL(srbd::pdipm_kernel, dim3(a.batch), dim3(srbd::kGeneralThreads), lds, s, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : set_error((int)e, "pdipm_kernel launch");
+  return launched("pdipm_srbd_reg_kernel launch");
 }
 
 // CusADi-style blocking call on the legacy default stream, timed with hipEvents (one event pair
@@ -312,7 +377,7 @@ float timed_blocking(F&& launch) {
   std::lock_guard<std::mutex> lock(mu);
   Events* ev = events.at(current_device());
   if (!ev) {
-    set_error((int)hipErrorInvalidDevice, "no current HIP device (or index >= 64)");
+    no_device();
     return -1.0f;
   }
   if (!ev->ev[0]) {
@@ -351,7 +416,7 @@ int srbd_set_solver_path(int path) {
   if (path < 0 || path > 2)
     return set_error(kErrInvalid, "srbd_set_solver_path: 0 (auto), 1 (general) or 2 (LDS-resident fast)");
   int* p = g_solver_path.at(current_device());
-  if (!p) return set_error((int)hipErrorInvalidDevice, "srbd_set_solver_path: no current HIP device");
+  if (!p) return no_device("srbd_set_solver_path");
   *p = path;
   return 0;
 }
@@ -362,7 +427,7 @@ int srbd_set_refinement(int mode) {
   if (mode < 0 || mode > 1)
     return set_error(kErrInvalid, "srbd_set_refinement: 0 (ill-conditioned iterates) or 1 (every iteration)");
   RefinePolicy* p = g_refinement.at(current_device());
-  if (!p) return set_error((int)hipErrorInvalidDevice, "srbd_set_refinement: no current HIP device");
+  if (!p) return no_device("srbd_set_refinement");
   *p = RefinePolicy{mode, 0, 0.0};
   return 0;
 }
@@ -373,7 +438,7 @@ int srbd_set_refinement_policy(int flags, double w) {
   if ((flags & ~known) != 0 || w != w)
     return set_error(kErrInvalid, "srbd_set_refinement_policy: unknown policy bits or a NaN threshold");
   RefinePolicy* p = g_refinement.at(current_device());
-  if (!p) return set_error((int)hipErrorInvalidDevice, "srbd_set_refinement_policy: no current HIP device");
+  if (!p) return no_device("srbd_set_refinement_policy");
   *p = RefinePolicy{2, flags, w};
   return 0;
 }
@@ -389,7 +454,7 @@ int srbd_release_device(void) {
   std::unique_lock<std::shared_mutex> no_launch(g_pool_rw);
   std::lock_guard<std::mutex> lock(g_scratch_mu);
   ScratchPool* pool = g_scratch.at(current_device());
-  if (!pool) return set_error((int)hipErrorInvalidDevice, "srbd_release_device: no current HIP device");
+  if (!pool) return no_device("srbd_release_device");
   return release_pool(pool);
 }
 
@@ -400,7 +465,7 @@ int srbd_set_scratch_slots(int slots) {
   const int dev = current_device();
   int* cap = g_scratch_cap.at(dev);
   ScratchPool* pool = g_scratch.at(dev);
-  if (!cap || !pool) return set_error((int)hipErrorInvalidDevice, "srbd_set_scratch_slots: no current HIP device");
+  if (!cap || !pool) return no_device("srbd_set_scratch_slots");
   *cap = slots;
   if (pool->buf) {  // re-sized on the next solver call (or srbd_prepare_device)
     int cus = 0;
@@ -427,8 +492,7 @@ size_t srbd_scratch_slot_bytes(void) { return sizeof(double) * (size_t)general_s
 
 size_t srbd_mpc_workspace_doubles(int horizon, int batch) {
   if (!horizon_ok(horizon) || batch < 0) return 0;
-  const size_t N = (size_t)horizon;
-  return (size_t)batch * (24 * N + 24 * N + (122 * N - 24) + 14 * N + 28 * N + 16 * N);
+  return QpLayout(horizon).doubles((size_t)batch);
 }
 
 float srbd_evaluate_qp_former(int horizon, const double* inputs[], double* work, double* outputs[],
@@ -469,14 +533,8 @@ int srbd_qp_former(int horizon, int batch, const double* const* inputs, double* 
     return set_error(kErrInvalid, "srbd_qp_former: bad arguments");
   if (batch == 0) return 0;  // empty batch: buffers may be null (zero-size allocations)
   srbd::FormerArgs a{};
-  for (int i = 0; i < 17; ++i) {
-    if (!inputs[i]) return set_error(kErrInvalid, "srbd_qp_former: null input");
-    a.in[i] = inputs[i];
-  }
-  for (int i = 0; i < 6; ++i) {
-    if (!outputs[i]) return set_error(kErrInvalid, "srbd_qp_former: null output");
-    a.out[i] = outputs[i];
-  }
+  if (int rc = copy_pointers("srbd_qp_former", "null input", a.in, inputs, 17)) return rc;
+  if (int rc = copy_pointers("srbd_qp_former", "null output", a.out, outputs, 6)) return rc;
   a.N = horizon;
   a.batch = batch;
   return launch_former(a, (hipStream_t)stream);
@@ -489,14 +547,8 @@ static int pdipm_common(int horizon, int n_iter, int batch, double y0, int init_
   if (batch == 0) return 0;
   srbd::SolverArgs a{};
   const int nin = init_mode == 0 ? 10 : init_mode == 2 ? 7 : 6;  // QP + iterate / + x_init / QP only
-  for (int i = 0; i < nin; ++i) {
-    if (!inputs[i]) return set_error(kErrInvalid, "srbd_pdipm: null input");
-    a.in[i] = inputs[i];
-  }
-  for (int i = 0; i < 6; ++i) {
-    if (!outputs[i]) return set_error(kErrInvalid, "srbd_pdipm: null output");
-    a.out[i] = outputs[i];
-  }
+  if (int rc = copy_pointers("srbd_pdipm", "null input", a.in, inputs, nin)) return rc;
+  if (int rc = copy_pointers("srbd_pdipm", "null output", a.out, outputs, 6)) return rc;
   a.N = horizon;
   a.n_iter = n_iter;
   a.batch = batch;
@@ -540,16 +592,12 @@ static int mpc_solve_two_kernels(int horizon, int n_iter, int batch, double y0, 
                                  double* qp_workspace, double* const* outputs, const srbd_solve_info* info,
                                  void* stream) {
   if (!horizon_ok(horizon) || !qp_workspace) return set_error(kErrInvalid, "srbd_mpc_solve: bad arguments");
-  const size_t N = (size_t)horizon, B = (size_t)(batch < 0 ? 0 : batch);
-  double* H = qp_workspace;
-  double* f = H + B * 24 * N;
-  double* A = f + B * 24 * N;
-  double* b = A + B * (122 * N - 24);
-  double* G = b + B * 14 * N;
-  double* d = G + B * 28 * N;
-  double* qp[6] = {H, f, A, b, G, d};
+  double* qp[6];
+  double* ws = qp_workspace;
+  QpLayout(horizon).carve(ws, (size_t)(batch < 0 ? 0 : batch), qp);
   if (int rc = srbd_qp_former(horizon, batch, former_inputs, qp, stream)) return rc;
-  const double* sin[10] = {H, G, A, f, d, b, nullptr, nullptr, nullptr, nullptr};
+  const double* sin[10] = {};  // a cold start: the QP alone
+  solver_order(qp, sin);
   return pdipm_common(horizon, n_iter, batch, y0, 1, sin, outputs, info, stream);
 }
 
@@ -559,30 +607,24 @@ int srbd_mpc_solve(int horizon, int n_iter, int batch, double y0, const double* 
 }
 
 // launch of the fused / controller-step kernel (a fully set up FusedArgs): the register kernels at
-// the horizons they are instantiated for (10, 20 and regN.hpp's), the LDS-resident one-launch step
-// (mpc_step_lds.hpp) at every other horizon
+// the horizons they are instantiated for, the LDS-resident one-launch step (mpc_step_lds.hpp) at every
+// other horizon
 static int launch_step(const srbd::FusedArgs& a0, hipStream_t st) {
-  static srbd::LdsAttr cfg_lds;
   srbd::FusedArgs a = a0;
   set_refinement_args(a);
-  if (srbd::regn::supported(a.N)) {
-    srbd::regn::launch_step(a.N, a, st);  // static LDS (RegLayout)
-  } else if (a.N != 10 && a.N != 20) {
-    const size_t lds = srbd::step_lds_bytes(a.N);
-    if (lds > 160 * 1024) return set_error(kErrInvalid, "horizon too large for the one-launch step");
-    if (int rc = ensure_lds_attr((const void*)srbd::mpc_step_lds_kernel<0>, lds, cfg_lds)) return rc;
-    hipLaunchKernelGGL(srbd::mpc_step_lds_kernel<0>, dim3(a.batch), dim3(64), lds, st, a);
-  } else if (a.N == 10) {
-    hipLaunchKernelGGL(srbd::mpc_step_reg_kernel<10>, dim3(a.batch), dim3(64), 0, st, a);
-  } else {
-#ifdef SRBD_SPLIT_REG20
-    srbd::reg20::launch_step(a, st);
-#else
-    hipLaunchKernelGGL(srbd::mpc_step_reg_kernel<20>, dim3(a.batch), dim3(srbd::reg_tpb(20)), 0, st, a);
-#endif
+  switch (serves(a.N)) {  // the register kernels' LDS is static (RegLayout)
+    case Serves::Lds: {
+      static LdsKernel step_lds{srbd::mpc_step_lds_kernel<0>, "mpc_step_lds_kernel launch",
+                                "horizon too large for the one-launch step"};
+      return launch_dynamic_lds(step_lds, 64, srbd::step_lds_bytes(a.N), a, st);
+    }
+    case Serves::Reg10:
+      hipLaunchKernelGGL(srbd::mpc_step_reg_kernel<10>, dim3(a.batch), dim3(64), 0, st, a);
+      break;
+    case Serves::Reg20: srbd::reg20::launch_step(a, st); break;
+    case Serves::RegN: srbd::regn::launch_step(a.N, a, st); break;
   }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : set_error((int)e, "mpc_step_reg_kernel launch");
+  return launched("mpc_step_reg_kernel launch");
 }
 
 int srbd_mpc_solve_fused_info(int horizon, int n_iter, int batch, double y0, const double* const* former_inputs,
@@ -596,17 +638,16 @@ int srbd_mpc_solve_fused_info(int horizon, int n_iter, int batch, double y0, con
   if (n_iter < 1 || batch < 0 || !former_inputs || !outputs)
     return set_error(kErrInvalid, "srbd_mpc_solve_fused: bad arguments");
   if (batch == 0) return 0;
-  const size_t N = (size_t)horizon, B = (size_t)batch;
   srbd::FusedArgs a{};
-  for (int i = 0; i < 17; ++i) {
-    if (!former_inputs[i]) return set_error(kErrInvalid, "srbd_mpc_solve_fused: null input");
-    a.in[i] = former_inputs[i];
-  }
+  if (int rc = copy_pointers("srbd_mpc_solve_fused", "null input", a.in, former_inputs, 17)) return rc;
   for (int i = 0; i < 6; ++i) a.out[i] = outputs[i];  // null: not written
-  if (qp_workspace) {  // same slots as srbd_mpc_solve's H, f, A, b, G, d
-    a.vec[0] = qp_workspace + B * 24 * N;
-    a.vec[1] = a.vec[0] + B * 24 * N + B * (122 * N - 24);
-    a.vec[2] = a.vec[1] + B * 14 * N + B * 28 * N;
+  if (qp_workspace) {  // the vectors f, b, d in the same slots as srbd_mpc_solve's H, f, A, b, G, d
+    double* qp[6];
+    double* ws = qp_workspace;
+    QpLayout(horizon).carve(ws, (size_t)batch, qp);
+    a.vec[0] = qp[1];
+    a.vec[1] = qp[3];
+    a.vec[2] = qp[5];
   }
   a.N = horizon;
   a.n_iter = n_iter;
@@ -634,10 +675,8 @@ static int fill_prep(const srbd_mpc_prep* p, srbd::PrepArgs& a, const char* who)
       !p->desired_height || !p->world_position_desired || !p->yaw_desired || !p->first_run || !p->dt_mpc ||
       !p->residual_lin_accel || !p->residual_ang_accel ||
       (p->gait_phase ? (!p->ssp_durations || !p->dsp_durations) : !p->contact_table) ||
-      (p->q_len != 12 && p->q_len != 13)) {
-    std::string w = std::string(who) + ": missing array or bad q_len";
-    return set_error(kErrInvalid, w.c_str());
-  }
+      (p->q_len != 12 && p->q_len != 13))
+    return fail(who, "missing array or bad q_len");
   a.root_euler = p->root_euler;
   a.root_position = p->root_position;
   a.ang_vel_w = p->root_angular_velocity_w;
@@ -683,10 +722,7 @@ int srbd_mpc_step_info(int horizon, int n_iter, int batch, double y0, const srbd
   a.prep.N = horizon;
   a.prep.batch = batch;
   if (former_inputs)
-    for (int i = 0; i < 17; ++i) {
-      if (!former_inputs[i]) return set_error(kErrInvalid, "srbd_mpc_step: null former_inputs entry");
-      a.prep.out[i] = former_inputs[i];
-    }
+    if (int rc = copy_pointers("srbd_mpc_step", "null former_inputs entry", a.prep.out, former_inputs, 17)) return rc;
   a.ctrl = 1;
   if (outputs)
     for (int i = 0; i < 6; ++i) a.out[i] = outputs[i];
@@ -726,8 +762,6 @@ int srbd_mpc_step(int horizon, int n_iter, int batch, double y0, const srbd_mpc_
 
 namespace {
 
-int fail(const char* what, const char* msg) { return set_error(kErrInvalid, (std::string(what) + ": " + msg).c_str()); }
-
 // batch * n_seeds gradient rows must fit the launch grid's int
 bool seed_rows_ok(int batch, int n_seeds) { return (long long)batch * (long long)n_seeds <= (long long)INT_MAX; }
 
@@ -761,7 +795,7 @@ int adjoint_impl(const char* what, bool x_only, int horizon, int batch, int n_se
   if (!any_seed(sd)) return fail(what, x_only ? "null grad_x" : "no seed given: all five cotangents are null");
   if (sd.grad_objective && !inputs[3]) return fail(what, "grad_objective needs f (input 3)");
   const size_t lds = srbd::backward_lds_bytes(horizon);
-  if (lds > 160 * 1024) return set_error(kErrInvalid, "horizon too large for the LDS-resident backward solve");
+  constexpr const char* kTooLarge = "horizon too large for the LDS-resident backward solve";
   auto fill = [&](auto& a) {  // the fields BackwardArgs and BackwardMultiArgs share
     for (int i = 0; i < 10; ++i) a.in[i] = inputs[i];
     a.grad_x = sd.grad_x;
@@ -775,23 +809,21 @@ int adjoint_impl(const char* what, bool x_only, int horizon, int batch, int n_se
   const bool full = sd.grad_s || sd.grad_z || sd.grad_y || sd.grad_objective;
   // one seed per env, B rows: the single-seed kernel (the other's bits, 1-2 % faster there)
   if (n_seeds == 1 && !sd.shared) {
-    static srbd::LdsAttr cfg_backward[2];
+    constexpr const char* kWhat = "pdipm_backward_kernel launch";
+    static LdsKernel<srbd::BackwardArgs> of_x{srbd::bwd::adjoint_kernel(false), kWhat, kTooLarge};
+    static LdsKernel<srbd::BackwardArgs> of_all{srbd::bwd::adjoint_kernel(true), kWhat, kTooLarge};
     srbd::BackwardArgs a{};
     fill(a);
-    if (int rc = ensure_lds_attr(srbd::bwd::adjoint_kernel(full), lds, cfg_backward[full])) return rc;
-    srbd::bwd::launch_adjoint(a, full, lds, (hipStream_t)stream);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_error((int)e, "pdipm_backward_kernel launch");
+    return launch_dynamic_lds(full ? of_all : of_x, 64, lds, a, (hipStream_t)stream);
   }
-  static srbd::LdsAttr cfg_backward_multi[2];
+  constexpr const char* kWhat = "pdipm_backward_multi_kernel launch";
+  static LdsKernel<srbd::BackwardMultiArgs> of_x{srbd::bwd::adjoint_multi_kernel(false), kWhat, kTooLarge};
+  static LdsKernel<srbd::BackwardMultiArgs> of_all{srbd::bwd::adjoint_multi_kernel(true), kWhat, kTooLarge};
   srbd::BackwardMultiArgs a{};
   fill(a);
   a.shared = sd.shared ? 1 : 0;
   a.n_seeds = n_seeds;
-  if (int rc = ensure_lds_attr(srbd::bwd::adjoint_multi_kernel(full), lds, cfg_backward_multi[full])) return rc;
-  srbd::bwd::launch_adjoint_multi(a, full, lds, (hipStream_t)stream);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : set_error((int)e, "pdipm_backward_multi_kernel launch");
+  return launch_dynamic_lds(full ? of_all : of_x, 64, lds, a, (hipStream_t)stream);
 }
 
 // the former's vector-Jacobian product over batch * n_seeds gradient rows
@@ -800,18 +832,14 @@ int former_vjp_impl(const char* what, int horizon, int batch, int n_seeds, const
   if (int rc = check_seeds(what, horizon, batch, n_seeds, 0, former_inputs && qp_grads && input_grads)) return rc;
   if (batch == 0) return 0;
   srbd::FormerBackwardArgs a{};
-  for (int i = 0; i < 17; ++i) {
-    if (!former_inputs[i]) return fail(what, "null input");
-    a.in[i] = former_inputs[i];
-    a.out[i] = input_grads[i];  // null: not written
-  }
+  if (int rc = copy_pointers(what, "null input", a.in, former_inputs, 17)) return rc;
+  for (int i = 0; i < 17; ++i) a.out[i] = input_grads[i];  // null: not written
   for (int i = 0; i < 6; ++i) a.g[i] = qp_grads[i];  // null: a zero gradient
   a.N = horizon;
   a.batch = batch;
   a.n_seeds = n_seeds;
   srbd::bwd::launch_former_backward(a, (hipStream_t)stream);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : set_error((int)e, "qp_former_backward_kernel launch");
+  return launched("qp_former_backward_kernel launch");
 }
 
 // the QP gradients (bit o: H, f, A, b, G, d) the gradient of former input i reads: the table in the
@@ -845,15 +873,6 @@ unsigned qp_grads_needed(unsigned input_mask) {
   return need;
 }
 
-void qp_widths(int horizon, size_t (&w)[6]) {  // H, f, A, b, G, d
-  const size_t N = (size_t)horizon;
-  w[0] = w[1] = 24 * N;
-  w[2] = 122 * N - 24;
-  w[3] = 14 * N;
-  w[4] = 28 * N;
-  w[5] = 16 * N;
-}
-
 // former -> adjoint -> former VJP. The workspace holds the QP, then the QP gradients the non-null
 // input_grads read, (B, M, width) each; the others are null to both kernels (the adjoint kernel skips a
 // null output, the VJP reads a null gradient as zero). Whether asking for no gradient at all is an error
@@ -871,22 +890,16 @@ int mpc_backward_impl(const char* what, bool x_only, bool need_request, int hori
     if (input_grads[i]) input_mask |= 1u << i;
   if (need_request && input_mask == 0) return fail(what, "no input gradient requested");
   const unsigned need = qp_grads_needed(input_mask);
-  const size_t B = (size_t)batch, M = (size_t)n_seeds;
-  size_t w[6];
-  qp_widths(horizon, w);
+  const QpLayout layout(horizon);
   double* qp[6];
   double* gr[6];
   double* o = workspace;
-  for (int i = 0; i < 6; ++i) {
-    qp[i] = o;
-    o += B * w[i];
-  }
-  for (int i = 0; i < 6; ++i) {
-    gr[i] = (need >> i & 1u) ? o : nullptr;
-    if (gr[i]) o += B * M * w[i];
-  }
+  layout.carve(o, (size_t)batch, qp);
+  layout.carve(o, (size_t)batch * (size_t)n_seeds, gr, need);
   if (int rc = srbd_qp_former(horizon, batch, former_inputs, qp, stream)) return rc;
-  const double* sin[10] = {qp[0], qp[4], qp[2], qp[1], qp[5], qp[3], iterate[0], iterate[1], iterate[2], iterate[3]};
+  const double* sin[10];
+  solver_order(qp, sin);
+  std::copy(iterate, iterate + 4, sin + 6);
   if (int rc = adjoint_impl(what, x_only, horizon, batch, n_seeds, sin, sd, gr, status, stream)) return rc;
   return former_vjp_impl(what, horizon, batch, n_seeds, former_inputs, gr, input_grads, stream);
 }
@@ -931,12 +944,9 @@ unsigned srbd_former_grad_deps(int input) { return input >= 0 && input < 17 ? kF
 
 size_t srbd_mpc_backward_multi_workspace_doubles(int horizon, int batch, int n_seeds, unsigned input_mask) {
   if (!horizon_ok(horizon) || batch < 0 || n_seeds < 1 || !seed_rows_ok(batch, n_seeds)) return 0;
-  size_t w[6];
-  qp_widths(horizon, w);
   const unsigned need = qp_grads_needed(input_mask ? input_mask : ~0u);  // 0 = all 17
-  size_t per_env = 0;
-  for (int o = 0; o < 6; ++o) per_env += w[o] + ((need >> o & 1u) ? (size_t)n_seeds * w[o] : 0);
-  return (size_t)batch * per_env;  // what mpc_backward_impl carves
+  const QpLayout layout(horizon);  // what mpc_backward_impl carves
+  return layout.doubles((size_t)batch) + layout.doubles((size_t)batch * (size_t)n_seeds, need);
 }
 
 size_t srbd_mpc_backward_workspace_doubles(int horizon, int batch) {
@@ -1038,8 +1048,7 @@ int wrench_vjp_impl(const char* what, int horizon, int batch, const double* x, c
   srbd::bwd::launch_wrench_backward(horizon, batch, x, rotation_body, grad_wrench, grad_tau ? ndof : 0,
                                     contact_jacobian, contact_bool, grad_tau, grad_x, grad_rotation_body,
                                     (hipStream_t)stream);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : set_error((int)e, "u0_wrench_backward_kernel launch");
+  return launched("u0_wrench_backward_kernel launch");
 }
 
 // the arrays of srbd_mpc_prep the prep VJP reads
@@ -1070,8 +1079,7 @@ int prep_vjp_impl(const char* what, int horizon, int batch, const srbd_mpc_prep*
   a.batch = batch;
   srbd::bwd::launch_prepare_backward(a, input_grads, grad_wpd_out, grad_yaw_out, grad_rotation_body_direct,
                                      prep_grads, (hipStream_t)stream);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : set_error((int)e, "prepare_inputs_backward_kernel launch");
+  return launched("prepare_inputs_backward_kernel launch");
 }
 
 size_t former_in_width(int i, int N) { return (size_t)srbd::former_in_nnz(i, N); }
@@ -1157,8 +1165,7 @@ int step_backward_impl(const char* what, bool with_cost, int horizon, int batch,
   if (grad_cost) {  // behind srbd_mpc_step_backward's layout: the cost cotangent, widened (B)
     double* gJ = o + srbd_mpc_backward_multi_workspace_doubles(horizon, batch, 1, need);
     srbd::bwd::launch_widen(batch, grad_cost, gJ, (hipStream_t)stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error((int)e, "widen_f32_kernel launch");
+    if (int rc = launched("widen_f32_kernel launch")) return rc;
     sd.grad_objective = gJ;
   }
   if (int rc = mpc_backward_impl(what, !with_cost, false, horizon, batch, 1, former_inputs, iterate, sd, mpc_ws,
@@ -1265,15 +1272,11 @@ int srbd_prepare_inputs(int horizon, int batch, const srbd_mpc_prep* p, double* 
   if (batch == 0) return 0;
   srbd::PrepArgs a{};
   if (int rc = fill_prep(p, a, "srbd_prepare_inputs")) return rc;
-  for (int i = 0; i < 17; ++i) {
-    if (!former_inputs[i]) return set_error(kErrInvalid, "srbd_prepare_inputs: null output");
-    a.out[i] = former_inputs[i];
-  }
+  if (int rc = copy_pointers("srbd_prepare_inputs", "null output", a.out, former_inputs, 17)) return rc;
   a.N = horizon;
   a.batch = batch;
   hipLaunchKernelGGL(srbd::prepare_inputs_kernel, dim3((batch + 3) / 4), dim3(256), 0, (hipStream_t)stream, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : set_error((int)e, "prepare_inputs_kernel launch");
+  return launched("prepare_inputs_kernel launch");
 }
 
 int srbd_u0_wrench(int horizon, int batch, const double* x, const float* rotation_body, float* foot_wrench,
@@ -1291,8 +1294,7 @@ int srbd_u0_wrench_torque(int horizon, int batch, const double* x, const float* 
   if (batch == 0) return 0;
   hipLaunchKernelGGL(srbd::u0_wrench_kernel, dim3((batch + 255) / 256), dim3(256), 0, (hipStream_t)stream, horizon,
                      batch, x, rotation_body, foot_wrench, ndof, contact_jacobian, contact_bool, tau);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : set_error((int)e, "u0_wrench_kernel launch");
+  return launched("u0_wrench_kernel launch");
 }
 
 int srbd_dense_scatter(int batch, int nnz, int rc, const int* inverse_index, const double* values, double* dense,
@@ -1303,8 +1305,7 @@ int srbd_dense_scatter(int batch, int nnz, int rc, const int* inverse_index, con
   if (batch == 0 || rc == 0) return 0;
   hipLaunchKernelGGL(srbd::dense_scatter_kernel, dim3((rc + 511) / 512, batch), dim3(256), 0, (hipStream_t)stream, rc,
                      nnz, batch, (const int32_t*)inverse_index, values, dense);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : set_error((int)e, "dense_scatter_kernel launch");
+  return launched("dense_scatter_kernel launch");
 }
 
 }  // extern "C"

@@ -7,8 +7,6 @@
 
 namespace srbd {
 namespace reg20 {
-const void* solver_kernel() { return (const void*)pdipm_srbd_reg_kernel<20>; }
-const void* step_kernel() { return (const void*)mpc_step_reg_kernel<20>; }
 void launch_solver(const SolverArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(pdipm_srbd_reg_kernel<20>, dim3(a.batch), dim3(reg_tpb(20)), 0, s, a);
 }

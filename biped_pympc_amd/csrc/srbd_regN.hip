@@ -43,33 +43,6 @@ bool supported(int N) {
   }
 }
 
-size_t lds_bytes(int N) {
-  switch (N) {
-#define SRBD_CASE(n) case n: return sizeof(double) * (size_t)RegLayout<n>::total;
-    SRBD_REGN_HORIZONS(SRBD_CASE)
-#undef SRBD_CASE
-    default: return 0;
-  }
-}
-
-const void* solver_kernel(int N) {
-  switch (N) {
-#define SRBD_CASE(n) case n: return (const void*)pdipm_srbd_reg_kernel<n>;
-    SRBD_REGN_HORIZONS(SRBD_CASE)
-#undef SRBD_CASE
-    default: return nullptr;
-  }
-}
-
-const void* step_kernel(int N) {
-  switch (N) {
-#define SRBD_CASE(n) case n: return (const void*)mpc_step_reg_kernel<n>;
-    SRBD_REGN_HORIZONS(SRBD_CASE)
-#undef SRBD_CASE
-    default: return nullptr;
-  }
-}
-
 void launch_solver(int N, const SolverArgs& a, hipStream_t s) {
   switch (N) {
 #define SRBD_CASE(n) \

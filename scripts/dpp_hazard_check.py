@@ -7,7 +7,7 @@ states, other instructions 1. The scan walks back along every control-flow prede
 fall-through instruction (unless it is an unconditional s_branch / s_endpgm / s_setpc) and every
 branch that targets a label it crosses.
 
-    hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -DSRBD_SPLIT_REG20 --cuda-device-only -S \
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude --cuda-device-only -S \
         -o /tmp/k.s biped_pympc_amd/csrc/srbd_mpc.hip
     python scripts/dpp_hazard_check.py /tmp/k.s [kernel-symbol-substring]
 """
